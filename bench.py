@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark: consensus-ADMM CSC learner on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line (the
+dominant kernel's roofline comes from the timed steps' own per-kernel timers).
+--dump-outputs DIR also writes what the learner returns after the last timed step.
+--full adds everything that takes runs of its own: the objective before and after,
+the measured streaming-copy rate, the 8-GPU rank-0 shard timed alone, the other
+BASELINE.json configs and the CPU baseline.
 
 Workload (BASELINE.json configs[1], "C2"): 2D dzParallel learning of K = 100
 filters 11x11 on n = 10,000 synthetic contrast-normalised 100x100 patches,
@@ -407,6 +414,32 @@ def configs_leg(local):
     return out
 
 
+DUMP_SAMPLE = 1 << 21   # elements kept of each large output (16 MiB as float64)
+
+
+def dump_outputs(sess, out_dir, rank, world):
+    """--dump-outputs: what a caller of the timed path receives after its last step
+    (Session.results: the filters d_res, the codes z_res and the reconstructions DZ of this
+    rank's patches), as float64 .npy files.  d is whole; z and DZ are DUMP_SAMPLE elements
+    each at fixed seeded positions of the column-major array (the same positions for the
+    same problem size).  Rank 0 writes d.npy, z_sample.npy and DZ_sample.npy; the other
+    ranks write their shards' samples as <name>.rank<r>.npy."""
+    d_res, z_res, DZ, _ = sess.results(want_z=True, want_DZ=True)   # collective: every rank
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    if rank == 0:
+        np.save(os.path.join(out_dir, "d.npy"), np.ascontiguousarray(d_res))
+    for name, a, seed in (("z_sample", z_res, 2017), ("DZ_sample", DZ, 2018)):
+        flat = a.reshape(-1, order="F")   # a view: results() returns column-major arrays
+        if flat.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(seed).integers(0, flat.size, DUMP_SAMPLE))
+            flat = flat[idx]
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(flat))
+    if rank == 0:
+        log(f"outputs after the last step written to {out_dir} "
+            f"(d {d_res.shape}, samples of z {z_res.shape} and DZ {DZ.shape})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -417,11 +450,20 @@ def main():
     ap.add_argument("--tol", type=float, default=0.0,
                     help="inner/outer tol (the reference driver's 1e-3, learn_kernels_2D_large.m:24;"
                          " the metric is defined at tol = 0: fixed inner counts)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the objective before and after (it must "
+                         "decrease), the measured streaming-copy rate for the roofline, the 8-GPU "
+                         "rank-0 shard timed alone, the C1/C3/C4/C5 timings and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the learner returns after its last "
+                         "step as DIR/<name>.npy (float64): the filters d, and a fixed seeded "
+                         "sample of the codes z and of the reconstructions DZ")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-shard-diag", action="store_true",
-                    help="skip the one-GPU timing of the 8-GPU rank-0 shard (13 blocks)")
+                    help="with --full: skip the one-GPU timing of the 8-GPU rank-0 shard (13 blocks)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the C1/C3/C4/C5 timings (one warm-up + three timed outer iterations each)")
+                    help="with --full: skip the C1/C3/C4/C5 timings (one warm-up + three timed "
+                         "outer iterations each)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -440,7 +482,8 @@ def main():
     from ccsc_code_iccv2017_amd import learners as E
     from ccsc_code_iccv2017_amd import synth
 
-    copy_gbs, copy_form = copy_rate(local)   # before the plan fills HBM
+    # --full: a run of its own, before the plan fills HBM
+    copy_gbs, copy_form = copy_rate(local) if args.full else (None, None)
     uid = None
     if world > 1:
         obj = [E.unique_id() if rank == 0 else None]
@@ -464,7 +507,8 @@ def main():
     ctx = E.Context(local, rank, world, uid)
     sess = E.Session(ctx, p, b)
     del b
-    obj_start = sess.objective()        # sanity: the learner must decrease it (outside timing)
+    # --full sanity: the learner must decrease the objective (outside timing)
+    obj_start = sess.objective() if args.full else None
 
     def barrier():
         if world > 1:
@@ -498,16 +542,19 @@ def main():
             kstats[name] = {"launches": n_, "avg_ms": ms_ / n_,
                             "alg_GBps": by_ / (ms_ / n_ * 1e-3) / 1e9}
     it = sess.iterlog()
-    obj = sess.objective()
+    obj = sess.objective() if args.full else None
+    if args.dump_outputs:
+        dump_outputs(sess, args.dump_outputs, rank, world)
     if rank == 0:
         log(f"per-kernel (rank 0): {json.dumps(kstats)}")
         if args.tol > 0:
             tr = it["trace"]
             log(f"tol {args.tol}: inner counts d {tr['n_d'].tolist()} z {tr['n_z'].tolist()}")
-        log(f"objective {obj_start:.6e} at start, {obj:.6e} after {sess.outer} outer iterations; "
-            f"tim_vals {it['tim_vals']}")
+        if args.full:
+            log(f"objective {obj_start:.6e} at start, {obj:.6e} after {sess.outer} outer "
+                f"iterations; tim_vals {it['tim_vals']}")
 
-    if rank == 0 and not (np.isfinite(obj) and obj < obj_start):
+    if args.full and rank == 0 and not (np.isfinite(obj) and obj < obj_start):
         log(f"WARNING: objective did not decrease: {obj_start:.6e} -> {obj:.6e}")
     avg_ms = zms / max(launches, 1)
     t_launch = avg_ms * 1e-3
@@ -533,6 +580,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": dt / max(done_steps, 1) * 1e3,
         "higher_is_better": True,
         "scaling": "strong",
@@ -561,7 +609,8 @@ def main():
             "frac": achieved / HBM_PEAK_GBS,
             # measured streaming copy on this GPU (read + write) and the kernel against it
             "copy_GBps": copy_gbs,
-            "copy_kernel": f"tools/copy_probe.hip, 16 B per lane, {copy_form}",
+            "copy_kernel": (f"tools/copy_probe.hip, 16 B per lane, {copy_form}"
+                            if args.full else None),
             "frac_of_copy": achieved / copy_gbs if copy_gbs else None,
             "traffic": traffic,
             "traffic_source": traffic_src,
@@ -580,7 +629,7 @@ def main():
     result["configs"] = None
     result["cpu_baseline"] = None
     result["shard8_diag"] = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         sess.close()
         ctx.close()
         if not args.no_shard_diag and args.n == 10000:

@@ -6,6 +6,7 @@ tag=$1; sel=$2
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/$tag
 python tools/check_lib.py || exit 1
+BENCH_ARGS="--full ${BENCH_ARGS:-}"   # the summary below reads the copy rate, shard and configs legs
 if [ -n "$sel" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v -k "$sel" --timeout 300 --timeout-method thread > gpurun_out/$tag/pytest.txt 2>&1 || { tail -30 gpurun_out/$tag/pytest.txt; exit 1; }
   tail -2 gpurun_out/$tag/pytest.txt

@@ -14,7 +14,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 B="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-configs --no-shard-diag"
 if [ "$2" != "nobench" ]; then
-  timeout -k 10 600 python3 bench.py > $out/bench.json 2> $out/bench.err || exit $?
+  timeout -k 10 600 python3 bench.py --full > $out/bench.json 2> $out/bench.err || exit $?
 fi
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $out/trace -o trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-configs --no-shard-diag > $out/trace.log 2>&1 || exit $?
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $out/fetch -o fetch -- $B > $out/fetch.log 2>&1 || exit $?
