@@ -290,10 +290,21 @@ template <typename T>
 hipError_t launch_max(const T* a, int64_t count, T* part, T* out, hipStream_t st);
 
 // ---- localcn.hip: CreateImages.m:299-369 'local_cn' + ZERO_MEAN (:652-657) ---------
-// n column-major [H, W] fp64 images (device pointers), one workgroup per image.
+// n column-major [H, W] fp64 images (device pointers).  LDS path: one workgroup per
+// image, shapes local_cn_ok accepts (at most 12288 pixels).
 bool local_cn_ok(int H, int W);
 hipError_t launch_local_cn(const double* in, double* out, int64_t n, int H, int W,
                            hipStream_t st);
+// Tiled path: many workgroups per image, any H, W >= 7 with H * W < 2^31
+// (local_cn_tiled_ok).  One launch serves m images over a workspace of
+// local_cn_tiled_ws_bytes(m, H, W) bytes, which must stay allocated until the stream has
+// run it; out may alias in.  local_cn_tiled_chunk: the images per launch, at most n, that
+// keep the workspace within budget bytes (one image when a single image exceeds it).
+bool local_cn_tiled_ok(int H, int W);
+size_t local_cn_tiled_ws_bytes(int64_t m, int H, int W);
+int64_t local_cn_tiled_chunk(int64_t n, int H, int W, size_t budget);
+hipError_t launch_local_cn_tiled(const double* in, double* out, int64_t m, int H, int W,
+                                 void* workspace, hipStream_t st);
 
 // ---- util.hip ---------------------------------------------------------------
 template <typename T>

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <limits>
@@ -650,6 +651,48 @@ struct Solver {
 
 using namespace ccsc;
 
+// ---- local contrast normalisation: argument checks and the choice of path ----------
+
+static void local_cn_check(const ccsc_ctx* ctx, const double* in, const double* out, int64_t n,
+                           int32_t H, int32_t W) {
+  if (!ctx || !in || !out || n < 0) throw Err(CCSC_E_INVALID, "bad arguments");
+  if (H < 7 || W < 7)
+    throw Err(CCSC_E_UNSUPPORTED,
+              "local_cn: H and W must be at least 7 pixels (the 13x13 window reflects 6 samples "
+              "per side)");
+  if (!local_cn_tiled_ok(H, W))
+    throw Err(CCSC_E_UNSUPPORTED, "local_cn: H * W must be below 2^31 pixels");
+}
+
+// n device images in -> out on the context's stream, synchronised on return.  The LDS
+// kernel where local_cn_ok holds, unless CCSC_CN_TILED=1; else the tiled path, in chunks
+// of images whose workspace stays within 256 MiB, or the CCSC_CN_WS_MB (MiB) below that
+// (0: one image per chunk; a single image larger than the budget still gets its own).
+// Both switches are read per call.
+static void local_cn_device(ccsc_ctx* ctx, const double* in, double* out, int64_t n, int32_t H,
+                            int32_t W) {
+  const char* et = std::getenv("CCSC_CN_TILED");
+  if (local_cn_ok(H, W) && !(et && et[0] == '1')) {
+    HIPCHK(launch_local_cn(in, out, n, H, W, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return;
+  }
+  if (n == 0) return;
+  size_t budget = (size_t)256 << 20;
+  if (const char* eb = std::getenv("CCSC_CN_WS_MB")) {
+    const long long mb = std::atoll(eb);
+    if (mb >= 0 && mb < 256) budget = (size_t)mb << 20;
+  }
+  const int64_t per = (int64_t)H * W;
+  const int64_t chunk = local_cn_tiled_chunk(n, H, W, budget);
+  DevBuf ws;
+  ws.alloc(local_cn_tiled_ws_bytes(chunk, H, W));
+  for (int64_t i0 = 0; i0 < n; i0 += chunk)
+    HIPCHK(launch_local_cn_tiled(in + i0 * per, out + i0 * per, std::min(chunk, n - i0), H, W,
+                                 ws.p, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));   // the workspace is released on return
+}
+
 extern "C" {
 
 int32_t ccsc_solve_supported(const ccsc_solve_problem* p, char* err, size_t errlen) {
@@ -676,21 +719,16 @@ int32_t ccsc_solve(ccsc_ctx* ctx, const ccsc_solve_problem* p, const ccsc_solve_
 int32_t ccsc_local_cn_dev(ccsc_ctx* ctx, const double* in, double* out, int64_t n, int32_t H,
                           int32_t W, char* err, size_t errlen) {
   return guarded(err, errlen, [&] {
-    if (!ctx || !in || !out || n < 0) throw Err(CCSC_E_INVALID, "bad arguments");
-    if (!local_cn_ok(H, W))
-      throw Err(CCSC_E_UNSUPPORTED, "local_cn: images must be 7x7 .. 12288 pixels and fit the LDS");
+    local_cn_check(ctx, in, out, n, H, W);
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(launch_local_cn(in, out, n, H, W, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    local_cn_device(ctx, in, out, n, H, W);
   });
 }
 
 int32_t ccsc_local_cn(ccsc_ctx* ctx, const double* in, double* out, int64_t n, int32_t H,
                       int32_t W, char* err, size_t errlen) {
   return guarded(err, errlen, [&] {
-    if (!ctx || !in || !out || n < 0) throw Err(CCSC_E_INVALID, "bad arguments");
-    if (!local_cn_ok(H, W))
-      throw Err(CCSC_E_UNSUPPORTED, "local_cn: images must be 7x7 .. 12288 pixels and fit the LDS");
+    local_cn_check(ctx, in, out, n, H, W);
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t per = (int64_t)H * W;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (256LL << 20) / (per * 8)));
@@ -701,7 +739,7 @@ int32_t ccsc_local_cn(ccsc_ctx* ctx, const double* in, double* out, int64_t n, i
       const int64_t m = std::min(chunk, n - i0);
       HIPCHK(hipMemcpyAsync(a.p, in + i0 * per, (size_t)(m * per) * 8, hipMemcpyHostToDevice,
                             ctx->stream));
-      HIPCHK(launch_local_cn(a.as<double>(), b.as<double>(), m, H, W, ctx->stream));
+      local_cn_device(ctx, a.as<double>(), b.as<double>(), m, H, W);
       HIPCHK(hipMemcpyAsync(out + i0 * per, b.p, (size_t)(m * per) * 8, hipMemcpyDeviceToHost,
                             ctx->stream));
     }

@@ -12,10 +12,12 @@ tests use seeded synthetic data of the same shapes:
     reference, the normalised image is stored as single then widened to double
     (CreateImages.m:367, :711).
 
-On a GPU the local contrast normalisation runs in libccsc's hand-written kernel
-(ccsc_local_cn_dev, csrc/localcn.hip: one workgroup per image, LDS-resident 13x13
-convolutions, radix-select median); the torch restatement below serves CPU tensors
-(tests, the CPU baseline).  PyTorch draws the synthetic codes and noise.
+On a GPU the local contrast normalisation of images of any size H, W >= 7 runs in
+libccsc's hand-written kernels (ccsc_local_cn_dev, csrc/localcn.hip, radix-select
+median): images of at most 12288 pixels in one workgroup each with LDS-resident 13x13
+convolutions, larger ones (real images, video frames) in 32 x 32 tiles over many
+workgroups per image.  The torch restatement below serves CPU tensors (tests, the CPU
+baseline).  PyTorch draws the synthetic codes and noise.
 """
 from __future__ import annotations
 
@@ -46,9 +48,16 @@ def rconv2(large: torch.Tensor, small: np.ndarray) -> torch.Tensor:
     return Fnn.conv2d(t, k[None, None])[:, 0]
 
 
+CN_TILE = 32   # tile edge of the tiled path (kCnTile in csrc/localcn.hip)
+
+
 def local_cn_gpu(imgs: torch.Tensor) -> torch.Tensor:
     """local_cn on the GPU through the C-ABI (ccsc_local_cn_dev); imgs [n, H, W] on a
-    CUDA device.  No fallback: a missing libccsc raises."""
+    CUDA device, any H, W >= 7 with H * W < 2^31 (smaller or larger raises CCSCError,
+    CCSC_E_UNSUPPORTED).  Shapes of at most 12288 pixels take the one-workgroup-per-image
+    LDS kernel, others the tiled kernels; CCSC_CN_TILED=1 in the environment forces the
+    tiled path, CCSC_CN_WS_MB lowers its 256 MiB workspace budget (images go in chunks).
+    No fallback: a missing libccsc raises."""
     from . import _lib as L
     from .learners import Context
     n, H, W = imgs.shape
@@ -67,8 +76,9 @@ def local_cn(imgs: torch.Tensor) -> torch.Tensor:
     """CreateImages.m:299-369 ('local_cn') then :652-657 (ZERO_MEAN) per image.
 
     imgs: [n, H, W] float64 (rows = MATLAB dim 1).  Returns float64 values that
-    went through the reference's single-precision storage.  CUDA tensors go through
-    the HIP kernel (local_cn_gpu); this torch restatement serves CPU tensors.
+    went through the reference's single-precision storage.  CUDA tensors of any
+    H, W >= 7 go through the HIP kernels (local_cn_gpu); this torch restatement serves
+    CPU tensors.
     """
     if imgs.is_cuda:
         return local_cn_gpu(imgs)

@@ -322,10 +322,22 @@ int32_t ccsc_solve(ccsc_ctx* ctx, const ccsc_solve_problem* p, const ccsc_solve_
  * Local contrast normalisation of the learners' input images: the 'local_cn' and
  * ZERO_MEAN branches of image_helpers/CreateImages.m:299-369, :652-657 (13x13 Gaussian,
  * sigma 3*1.591, reflection padding of image_helpers/rconv2.m:22-58, std floored at
- * its median, single-precision result), one GPU workgroup per image.
+ * its median, single-precision result), for images and frames of any size:
+ * H, W >= 7 and H * W < 2^31, anything else is CCSC_E_UNSUPPORTED with the reason.
  * in/out: n column-major [H, W] float64 images (out = double(single(...)), may alias in).
  * ccsc_local_cn takes host arrays; ccsc_local_cn_dev device arrays on the context's
- * device (e.g. torch tensors), ordered on the context's stream, synchronised on return. */
+ * device (e.g. torch tensors), ordered on the context's stream, synchronised on return.
+ * Two GPU paths, chosen by shape: images of at most 12288 pixels (110 x 110) whose
+ * padded (H+12) x (W+12) image fits the LDS run one workgroup per image; others run tiled, many
+ * workgroups per image (32 x 32 tiles, radix-select median over global memory).  Both
+ * share the 13x13 accumulate, so local mean, local std and the median floor are the same
+ * bits on either path; the results can differ by the single-precision rounding of the
+ * mean.  Each image's result is bitwise reproducible and independent of the batch.
+ * The tiled path allocates its workspace inside the call (16 B per pixel + 48 KiB per
+ * image) and frees it before returning; images go in chunks so that it stays within
+ * 256 MiB whatever n is (a single image larger than that still gets its own).
+ * Environment, read per call: CCSC_CN_TILED=1 forces the tiled path on any shape;
+ * CCSC_CN_WS_MB=<MiB> lowers the workspace budget (0: one image per chunk). */
 int32_t ccsc_local_cn(ccsc_ctx* ctx, const double* in, double* out, int64_t n, int32_t H,
                       int32_t W, char* err, size_t errlen);
 int32_t ccsc_local_cn_dev(ccsc_ctx* ctx, const double* in, double* out, int64_t n, int32_t H,
