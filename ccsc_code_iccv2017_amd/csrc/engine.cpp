@@ -246,9 +246,12 @@ static void resolve_problem(ccsc_problem& p) {
     case CCSC_DZPAR: mid = 5; rd = 5000; rz = 1; td = 1; break;  // dZ:75,99,151,154
     case CCSC_L3D:
     case CCSC_L4D: {
+      // the square root only defines the DEFAULT block size: a caller's own ni (a multiple
+      // check below) takes any n, e.g. three blocks of two patches
       const int64_t s = (int64_t)std::llround(std::sqrt((double)p.n));
-      if (s * s != p.n)
-        throw Err(CCSC_E_INVALID, "3D/4D learners need n to be a perfect square (ni = sqrt(n), L3:11)");
+      if (p.ni <= 0 && s * s != p.n)
+        throw Err(CCSC_E_INVALID, "3D/4D learners need n to be a perfect square (ni = sqrt(n), L3:11) "
+                                  "unless ni is given");
       ni = (int)s;
       if (p.variant == CCSC_L3D) { rd = 5000; rz = 1; td = 1; }  // L3:109,168,175
       break;                                                      // L4:105,159,162
@@ -1874,9 +1877,12 @@ struct SessionHS {
     HIPCHK(hipMemsetAsync(eD.p, 0, eD.bytes, st));
     HIPCHK(hipMemsetAsync(eZ.p, 0, eZ.bytes, st));
     HIPCHK(hipMemsetAsync(eZ2.p, 0, eZ2.bytes, st));
-    // codes z = randn(size_z) (L23:69)
+    // codes z = randn(size_z) (L23:69): this rank's images of the one global stream, so
+    // the draw does not depend on the rank count
     if (z0) HIPCHK(hipMemcpy(z.p, z0, z.bytes, hipMemcpyHostToDevice));
-    else HIPCHK(launch_randn<double>(z.as<double>(), (int64_t)zkn, p.seed, 0, st));
+    else
+      HIPCHK(launch_randn<double>(z.as<double>(), (int64_t)zkn, p.seed,
+                                  (uint64_t)i0 * (uint64_t)K * (uint64_t)P, st));
     // d_hat = fft2(d) (L23:57); u_D{2} of the first d-iteration = Pi(d - 0) (L23:113)
     r2c_full(D.as<double>(), Dh.as<cpx<double>>(), KG);
     HIPCHK(launch_gather_support<double>(D.as<double>(), yD.as<double>(), supp.as<double>(), KG, r,
@@ -2413,6 +2419,9 @@ int32_t ccsc_plan_bytes(const ccsc_problem* p, int32_t rank, int32_t nranks, uin
     Geom g;
     check_supported(q, &g);
     if (q.variant == CCSC_HS23) {
+      if (nranks > 1 && q.K > 192)   // as the SessionHS constructor: no size for what cannot run
+        throw Err(CCSC_E_UNSUPPORTED, "the 2-3D learner past K = 192 (the n x n Woodbury factor "
+                                      "couples every image) runs on one rank");
       int64_t i0 = 0, nl = 0;
       shard(q, rank, nranks, i0, nl);
       *bytes = plan_hs(q, g, nl, nranks > 1).total();

@@ -377,21 +377,34 @@ def _learn_2d(variant, b, kernel_size, lambda_residual, lambda_prior, max_it, to
     return d_res, z_res, DZ, iterations
 
 
-def learn_once(ctx, p, b, d0=None, z0=None, want_z=True, want_DZ=True):
+def learn_once(ctx, p, b, d0=None, z0=None, want_z=True, want_DZ=True, want_obj=False):
     """One ccsc_learn call over the whole problem (the MEX path): on a multi-device
-    context the engine shards it over the devices.  2D learners; returns
-    (d_res, z_res, DZ, iterations) like the session path."""
+    context the engine shards it over the devices.  The consensus learners (2D, 3D, 4D),
+    with the output shapes of Session.results over all n patches; returns
+    (d_res, z_res, DZ, iterations) like the session path, iterations['obj_val'] being the
+    final objective (the 3D / 4D learners' obj_val) when ``want_obj``."""
     p = resolve(p)
+    if p.variant == L.CCSC_HS23:
+        raise ValueError("the 2-3D learner takes smooth_init: use a Session")
     psf, K = p.psf, p.K
     r = psf // 2
     X, Y = p.sb[0] + 2 * r, p.sb[1] + 2 * r
     b = np.asfortranarray(b, dtype=np.float64)
     d0 = None if d0 is None else np.asfortranarray(d0, dtype=np.float64)
     z0 = None if z0 is None else np.asfortranarray(z0, dtype=np.float64)
-    d_res = np.zeros((psf, psf, K), order="F")
-    z_res = np.zeros((X, Y, K, p.n), order="F") if want_z else None
-    DZ = np.zeros((X, Y, 1, p.n), order="F") if want_DZ else None
-    out = L.Outputs(L.dptr(d_res), L.dptr(z_res), L.dptr(DZ), L.dptr(None))
+    if p.variant == L.CCSC_L3D:
+        T = p.sb[2] + 2 * r
+        sd, sz, sx = (psf, psf, psf, K), (X, Y, T, K, p.n), (X, Y, T, p.n)
+    elif p.variant == L.CCSC_L4D:
+        U, V = p.views[0], p.views[1]
+        sd, sz, sx = (psf, psf, U, V, K), (X, Y, 1, 1, K, p.n), (p.sb[0], p.sb[1], U, V, p.n)
+    else:
+        sd, sz, sx = (psf, psf, K), (X, Y, K, p.n), (X, Y, 1, p.n)
+    d_res = np.zeros(sd, order="F")
+    z_res = np.zeros(sz, order="F") if want_z else None
+    DZ = np.zeros(sx, order="F") if want_DZ else None
+    obj = np.zeros(1) if want_obj else None
+    out = L.Outputs(L.dptr(d_res), L.dptr(z_res), L.dptr(DZ), L.dptr(obj))
     cap = p.max_it + 1
     a = {k: np.full(cap, np.nan) for k in ("obj_vals_d", "obj_vals_z", "tim_vals")}
     tr = {"d_diff": np.full(cap * p.max_it_d, np.nan), "z_diff": np.full(cap * p.max_it_z, np.nan)}
@@ -409,6 +422,8 @@ def learn_once(ctx, p, b, d0=None, z0=None, want_z=True, want_DZ=True):
     it["trace"] = {"d_diff": tr["d_diff"][: nout * p.max_it_d].reshape(nout, p.max_it_d),
                    "z_diff": tr["z_diff"][: nout * p.max_it_z].reshape(nout, p.max_it_z),
                    "n_d": nd[:nout].copy(), "n_z": nz[:nout].copy()}
+    if want_obj:
+        it["obj_val"] = float(obj[0])
     return d_res, z_res, DZ, it
 
 
@@ -424,6 +439,25 @@ def admm_learn_conv2D_large_dzParallel(b, kernel_size, lambda_residual, lambda_p
     """Drop-in for 2D/admm_learn_conv2D_large_dzParallel.m:1-206."""
     return _learn_2d(L.CCSC_DZPAR, b, kernel_size, lambda_residual, lambda_prior, max_it, tol,
                      verbose, init, **kw)
+
+
+def _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ):
+    """The 3D / 4D learners' run: a session stepped to the end on one device, one
+    ccsc_learn over the whole problem on a multi-device context (as _learn_2d)."""
+    if ctx.group:
+        d_res, z_res, DZ, log = learn_once(ctx, p, b, d0, z0, want_z=want_z, want_DZ=want_DZ,
+                                           want_obj=True)
+        return d_res, z_res, DZ, log["obj_val"], log
+    s = Session(ctx, p, b, d0, z0)
+    try:
+        done = False
+        while s.outer < s.p.max_it and not done:
+            done = s.step(1)
+        d_res, z_res, DZ, obj = s.results(want_z=want_z, want_DZ=want_DZ, want_obj=True)
+        log = s.iterlog()
+    finally:
+        s.close()
+    return d_res, z_res, DZ, obj, log
 
 
 def admm_learn_conv4D_lightfield(b, kernel_size, lambda_residual, lambda_prior, max_it, tol,
@@ -454,15 +488,7 @@ def admm_learn_conv4D_lightfield(b, kernel_size, lambda_residual, lambda_prior, 
             z0 = init.get("z")
             if z0 is not None:
                 z0 = np.real(np.asarray(z0))
-        s = Session(ctx, p, b, d0, z0)
-        try:
-            done = False
-            while s.outer < s.p.max_it and not done:
-                done = s.step(1)
-            d_res, z_res, DZ, obj = s.results(want_z=want_z, want_DZ=want_DZ, want_obj=True)
-            log = s.iterlog()
-        finally:
-            s.close()
+        d_res, z_res, DZ, obj, log = _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ)
     finally:
         if own:
             ctx.close()
@@ -496,15 +522,7 @@ def admm_learn_conv3D_large(b, kernel_size, lambda_residual, lambda_prior, max_i
         if init is not None and len(init) > 0:
             d0 = init.get("d")
             z0 = init.get("z")
-        s = Session(ctx, p, b, d0, z0)
-        try:
-            done = False
-            while s.outer < s.p.max_it and not done:
-                done = s.step(1)
-            d_res, z_res, DZ, obj = s.results(want_z=want_z, want_DZ=want_DZ, want_obj=True)
-            log = s.iterlog()
-        finally:
-            s.close()
+        d_res, z_res, DZ, obj, log = _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ)
     finally:
         if own:
             ctx.close()

@@ -100,7 +100,8 @@ typedef struct ccsc_problem {
   double tol;               /* relative-change tolerance; <= 0 disables the tests   */
   int32_t verbose;          /* CCSC_VERBOSE_*                                       */
   /* internal constants of the learners; 0 / <= 0 selects the variant default   */
-  int32_t ni;               /* patches per block (dP:11 = 100, L3:11 = sqrt(n))     */
+  int32_t ni;               /* patches per block (dP:11 = 100, L3:11 = sqrt(n): the
+                               3D/4D default needs a square n, a given ni does not) */
   int32_t max_it_d;         /* dP:75                                                */
   int32_t max_it_z;         /* dP:76                                                */
   double rho_d;             /* dP:98,111                                            */
@@ -154,10 +155,13 @@ int32_t ccsc_supported(const ccsc_problem* p, char* err, size_t errlen);
 /* Blocks [*block_begin, *block_begin + *block_count) of ni patches go to `rank`.  The 2-3D
  * learner (one block of all n images, L23) shards single images: its "blocks" are images; on
  * several ranks each passes its images' b / smooth_init / z0 with the global n in the problem,
- * and every rank holds the same filters (the Gram Z'Z and Z'xi1 are summed over the ranks). */
+ * and every rank holds the same filters (the Gram Z'Z and Z'xi1 are summed over the ranks).
+ * The 2-3D learner with K > 192 runs on one rank only: with nranks > 1 its session and
+ * ccsc_plan_bytes return CCSC_E_UNSUPPORTED. */
 int32_t ccsc_shard(const ccsc_problem* p, int32_t rank, int32_t nranks,
                    int64_t* block_begin, int64_t* block_count, char* err, size_t errlen);
-/* Device bytes one rank needs for this problem. */
+/* Device bytes one rank needs for this problem (CCSC_E_UNSUPPORTED where no session of
+ * that rank count would run it). */
 int32_t ccsc_plan_bytes(const ccsc_problem* p, int32_t rank, int32_t nranks,
                         uint64_t* bytes, char* err, size_t errlen);
 
@@ -215,7 +219,10 @@ int32_t ccsc_learn(ccsc_ctx* ctx, const ccsc_problem* p, const double* b, const 
  * (L23:54-56), or NULL; z0: [X, Y, K, n] or NULL (device RNG from p->seed).
  * Outputs: d_res [psf,psf,W,K]; z_res [X,Y,K,n]; DZ [X,Y,W,n] = Dz incl. smoothinit,
  * uncropped (L23:234-235); obj_val = the last objective evaluated (L23:195 / :211).
- * One rank only (its d-solve couples every image per frequency). */
+ * Several ranks (one rank context of ccsc_create / ccsc_create_hostcomm per process, not a
+ * ccsc_create_multi device list): each passes its images (ccsc_shard) with the global n in
+ * the problem and z0 = NULL draws its images' part of the one global stream; K <= 192 only
+ * (past it the n x n Woodbury factor couples every image: one rank). */
 int32_t ccsc_learn_hs23(ccsc_ctx* ctx, const ccsc_problem* p, const double* b,
                         const double* smooth_init, const double* d0, const double* z0,
                         ccsc_outputs* out, ccsc_iterlog* log, ccsc_cb cb, void* user, char* err,

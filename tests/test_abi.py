@@ -77,6 +77,20 @@ def test_invalid_shapes_are_errors(L):
         resolve(p)                          # Q9: U != V
 
 
+def test_3d_4d_given_ni_takes_any_multiple(L):
+    """sqrt(n) is the 3D / 4D learners' DEFAULT block size (L3:11); a caller's own ni needs
+    only n % ni == 0, e.g. three blocks of two clips (the sharded tests' 2 + 1 split)."""
+    from ccsc_code_iccv2017_amd.learners import resolve, shard
+    for variant, sb in ((2, (8, 9, 7)), (3, (10, 9))):
+        with pytest.raises(L.CCSCError):
+            resolve(_problem(L, variant, sb=sb, n=6, K=3, psf=3))
+        q = resolve(_problem(L, variant, sb=sb, n=6, K=3, psf=3, ni=2))
+        assert q.ni == 2
+        assert [shard(q, r, 2) for r in range(2)] == [(0, 2), (2, 1)]
+        with pytest.raises(L.CCSCError):
+            resolve(_problem(L, variant, sb=sb, n=6, K=3, psf=3, ni=4))   # Q13 still holds
+
+
 def test_precision_codes(L):
     """ABI 7: CCSC_FP32 stays a (deprecated) name and reports UNSUPPORTED, any other value
     than CCSC_FP64 is INVALID (the removal was an ABI change)."""
@@ -226,3 +240,22 @@ def test_4d_many_filter_views_supported(L, K, UV, n):
     p = _problem(L, 3, sb=(64, 64), n=n, K=K)
     p.views[0] = p.views[1] = UV
     assert L.lib().ccsc_supported(C.byref(p), eb, len(eb)) == 0, eb.value
+
+
+def test_hs23_plan_bytes_rejects_what_its_session_rejects(L):
+    """The 2-3D learner past K = 192 runs on one rank (its n x n Woodbury factor couples
+    every image) and the session constructor says so; ccsc_plan_bytes must not size a run
+    that cannot start."""
+    from ccsc_code_iccv2017_amd.learners import plan_bytes
+
+    def hs(K):
+        p = _problem(L, 4, sb=(12, 11), n=4, K=K, psf=5)
+        p.views[0] = 3
+        return p
+    with pytest.raises(L.CCSCError) as ei:
+        plan_bytes(hs(200), 0, 2)
+    assert ei.value.code == L.CCSC_E_UNSUPPORTED and "one rank" in str(ei.value)
+    with pytest.raises(L.CCSCError):
+        plan_bytes(hs(200), 1, 2)
+    assert plan_bytes(hs(200), 0, 1) > 0
+    assert 0 < plan_bytes(hs(192), 0, 2) < plan_bytes(hs(192), 0, 1)

@@ -3,7 +3,15 @@
 all-reduce, per-outer broadcast of block 1's filter spectrum, tol norms)
 through the C-ABI, with the exchanges carried by the host-staged transport
 over gloo.  Must equal the single-rank engine and the oracle.  (8-GPU RCCL runs
-are the driver's; RCCL differs only in the transport calls.)"""
+are the driver's; RCCL differs only in the transport calls.)
+
+Every learner is here: the 2D learners and the 2-3D learner from explicit inits, the 3D and
+4D learners sharded 2 + 1 blocks (device list and sessions, LDS-resident and global-pass
+grids), and every learner from the device RNG (init = None), where the sharded draw must be
+the one-rank draw (tests/rng_ref.py restates the stream).  The spawned 3D / 4D and
+device-RNG cases share one process pair (fixture pair_dir).  Not covered: launch_randn's
+chunk boundary at 2^30 elements, which needs more than 8.6 GB of draws on the host to
+observe; by reading, its `out + c0` and `offset + c0` advance together."""
 import os
 import socket
 
@@ -341,3 +349,325 @@ def test_hs23_two_ranks_equal_oracle(tmp_path, gpu_ctx, K):
             np.testing.assert_allclose(q["od"][i], tr_o["obj_d"][i], rtol=1e-9)
     np.testing.assert_allclose(z, z_o, rtol=0, atol=1e-8 * np.abs(z_o).max())
     np.testing.assert_allclose(Dz, Dz_o, rtol=0, atol=1e-8 * np.abs(Dz_o).max())
+
+
+# ---------------------------------------------------------------------------
+# The 3D / 4D learners sharded, and the device RNG under sharding
+# ---------------------------------------------------------------------------
+def _rel(a, b):
+    return np.linalg.norm((a - b).ravel()) / np.linalg.norm(b.ravel())
+
+
+# three blocks over two ranks (2 + 1): the ranks differ in size
+# name: (variant, sb, views per axis, psf, K, n, ni, lambda_prior, max_it, tol)
+_ND = {
+    "L3": ("L3", (8, 9, 7), 1, 3, 3, 6, 2, 0.1, 2, 0.0),
+    "L3-tol": ("L3", (10, 10, 6), 1, 5, 4, 9, 3, 0.1, 3, 2e-2),   # test_learn_3d_matches_oracle's
+    "L4": ("L4", (10, 9), 2, 5, 3, 6, 2, 1.0, 2, 0.0),
+    "L4-3x3": ("L4", (9, 9), 3, 5, 2, 9, 3, 1.0, 2, 0.0),
+}
+_nd_cache = {}
+
+
+def _nd_case(name):
+    """(b, kernel_size, init, learner arguments) of a small sharded 3D / 4D case."""
+    v, sb, UV, psf, K, n, ni, lam, max_it, tol = _ND[name]
+    rng = np.random.default_rng(41)
+    r = psf // 2
+    g = tuple(s + 2 * r for s in sb)
+    if v == "L3":
+        b = rng.standard_normal(sb + (n,))
+        ks = [psf, psf, psf, K]
+        init = {"d": rng.standard_normal((psf, psf, psf, K)), "z": rng.standard_normal(g + (K, n))}
+    else:
+        b = rng.standard_normal(sb + (UV, UV, n))
+        ks = [psf, psf, UV, UV, K]
+        init = {"d": rng.standard_normal((psf, psf, UV, UV, K)),
+                "z": rng.standard_normal(g + (1, 1, K, n))}
+    return v, b, ks, init, (1.0, lam, max_it, tol, "brief"), ni
+
+
+def _nd_oracle(name):
+    """The float64 oracle of a case, computed once for the tests that share it."""
+    if name not in _nd_cache:
+        from oracle import ccsc_oracle as O
+        v, b, ks, init, args, ni = _nd_case(name)
+        fn = O.learn_3d if v == "L3" else O.learn_4d
+        d, z, DZ, obj, _, tr = fn(b, ks, *args, init, ni=ni, trace_objective=True)
+        for a in (d, z, DZ):
+            a.setflags(write=False)
+        _nd_cache[name] = (d, np.real(z), DZ, obj, tr)
+    return _nd_cache[name]
+
+
+def _nd_learn(name, ctx, init="case", **kw):
+    from ccsc_code_iccv2017_amd import learners as E
+    v, b, ks, init_c, args, ni = _nd_case(name)
+    fn = E.admm_learn_conv3D_large if v == "L3" else E.admm_learn_conv4D_lightfield
+    d, z, DZ, obj, it = fn(b, ks, *args, init_c if init == "case" else init, ni=ni, ctx=ctx, **kw)
+    return d, np.real(z), DZ, obj, it
+
+
+def _assert_close(got, want, bar):
+    for g, w in zip(got, want):
+        np.testing.assert_allclose(g, w, rtol=0, atol=bar * np.abs(w).max())
+
+
+@pytest.mark.parametrize("name", list(_ND))
+def test_multi_device_3d_4d_equal_oracle(gpu_ctx, name):
+    """The 3D and 4D learners on a multi-device context: learn_group's offsets for these
+    variants (b patches with the views and sb[2], z patches of K P, the cropped 4D DZ against
+    the uncropped 3D one, K U V psf^2 filter scratch on the ranks past 0) -- equal to the
+    oracle on the whole problem at the one-rank bars, and to the one-device engine."""
+    from ccsc_code_iccv2017_amd import learners as E
+    tol = _ND[name][-1]
+    d_o, z_o, DZ_o, obj_o, tr_o = _nd_oracle(name)
+    d1, z1, DZ1, obj1, it1 = _nd_learn(name, gpu_ctx)
+    mctx = E.Context.multi([0, 0])
+    try:
+        d2, z2, DZ2, obj2, it2 = _nd_learn(name, mctx)
+    finally:
+        mctx.close()
+    assert d2.shape == d_o.shape and z2.shape == z_o.shape and DZ2.shape == DZ_o.shape
+    assert _rel(d2, d_o) < 1e-7
+    assert _rel(z2, z_o) < 1e-7
+    assert _rel(DZ2, DZ_o) < 1e-7
+    assert abs(obj2 - obj_o) <= 1e-9 * abs(obj_o)
+    if tol > 0:
+        np.testing.assert_array_equal(it2["trace"]["n_d"], np.array(tr_o["n_d"]))
+        np.testing.assert_array_equal(it2["trace"]["n_z"], np.array(tr_o["n_z"]))
+    _assert_close((d2, z2, DZ2), (d1, z1, DZ1), 1e-10)
+    assert abs(obj2 - obj1) <= 1e-10 * abs(obj1)
+    np.testing.assert_array_equal(it2["trace"]["n_d"], it1["trace"]["n_d"])
+    np.testing.assert_array_equal(it2["trace"]["n_z"], it1["trace"]["n_z"])
+
+
+@pytest.mark.parametrize("variant", ["L3", "L4"])
+def test_multi_device_3d_4d_global_pass_equal_one_device(gpu_ctx, variant):
+    """Sharded 3D / 4D learns on grids past one CU's LDS (the global line passes), two blocks
+    over two ranks, against the one-device engine -- which test_learn_3d_grids_past_lds_match_
+    oracle and test_learn_4d_grid_past_lds_matches_oracle pin to the oracle on these very
+    inputs (tol > 0: the sharded change norms stop the inner loops at the same counts)."""
+    from ccsc_code_iccv2017_amd import learners as E
+    if variant == "L3":
+        rng = np.random.default_rng(29)
+        sb, psf, K, n = (150, 150, 4), 3, 2, 4
+        g = tuple(s + 2 * (psf // 2) for s in sb)
+        b = rng.standard_normal(sb + (n,))
+        init = {"d": rng.standard_normal((psf, psf, psf, K)), "z": rng.standard_normal(g + (K, n))}
+        fn, args = E.admm_learn_conv3D_large, (b, [psf] * 3 + [K], 1.0, 0.1, 2, 5e-2, "all", init)
+    else:
+        rng = np.random.default_rng(21)
+        sb, UV, psf, K, n = (150, 150), 2, 11, 3, 4
+        r = psf // 2
+        b = rng.standard_normal(sb + (UV, UV, n))
+        init = {"d": rng.standard_normal((psf, psf, UV, UV, K)),
+                "z": rng.standard_normal((sb[0] + 2 * r, sb[1] + 2 * r, 1, 1, K, n))}
+        fn, args = (E.admm_learn_conv4D_lightfield,
+                    (b, [psf, psf, UV, UV, K], 1.0, 1.0, 2, 1e-3, "all", init))
+    d1, z1, DZ1, obj1, it1 = fn(*args, ni=2, ctx=gpu_ctx)
+    mctx = E.Context.multi([0, 0])
+    try:
+        d2, z2, DZ2, obj2, it2 = fn(*args, ni=2, ctx=mctx)
+    finally:
+        mctx.close()
+    _assert_close((d2, z2.real, DZ2), (d1, z1.real, DZ1), 1e-10)
+    assert abs(obj2 - obj1) <= 1e-10 * abs(obj1)
+    np.testing.assert_array_equal(it2["trace"]["n_d"], it1["trace"]["n_d"])
+    np.testing.assert_array_equal(it2["trace"]["n_z"], it1["trace"]["n_z"])
+
+
+# dP with ONE patch per block on an 11 x 9 patch: K P = 3 * 15 * 13 = 585, so rank 1's
+# codes start at the odd stream element 585 -- the sine half of a Box-Muller pair
+_ODD = dict(sb=(11, 9), psf=5, K=3, ni=1, n=2)
+# name: (variant, sb, views per axis, psf, K, n, ni, lambda_prior)
+_RNG = {
+    "dP": ("dp", (12, 11), 1, 5, 3, 6, 2, 1.0),
+    "dP-odd": ("dp", _ODD["sb"], 1, _ODD["psf"], _ODD["K"], _ODD["n"], _ODD["ni"], 1.0),
+    # (dZ and 3D: theta_div = 1, so lambda_prior = 1 thresholds the small grids' codes to
+    # ~1e-7 and leaves nothing to compare)
+    "dZ": ("dz", (12, 11), 1, 5, 3, 6, 2, 0.1),
+    "L3": ("L3", (8, 9, 7), 1, 3, 3, 6, 2, 0.1),
+    "L4": ("L4", (10, 9), 2, 5, 3, 6, 2, 1.0),
+}
+
+
+@pytest.mark.parametrize("name", list(_RNG))
+def test_device_rng_init_is_shard_invariant(gpu_ctx, name):
+    """init = None: every rank of a multi-device learn draws its patches' part of the one
+    global code stream (offset = first local patch * K * P; dZ: the one block draw, on every
+    rank) and the same filters, so two outer iterations from the device draw end where the
+    one-device learn with the same seed ends."""
+    from ccsc_code_iccv2017_amd import learners as E
+    v, sb, UV, psf, K, n, ni, lam = _RNG[name]
+    b = np.random.default_rng(43).standard_normal(sb + ((UV, UV) if v == "L4" else ()) + (n,))
+    fn, ks = {"dp": (E.admm_learn_conv2D_large_dParallel, [psf, psf, K]),
+              "dz": (E.admm_learn_conv2D_large_dzParallel, [psf, psf, K]),
+              "L3": (E.admm_learn_conv3D_large, [psf, psf, psf, K]),
+              "L4": (E.admm_learn_conv4D_lightfield, [psf, psf, UV, UV, K])}[v]
+    args = (b, ks, 1.0, lam, 2, 0.0, "brief", None)
+    one = fn(*args, ni=ni, seed=977, ctx=gpu_ctx)
+    mctx = E.Context.multi([0, 0])
+    try:
+        two = fn(*args, ni=ni, seed=977, ctx=mctx)
+        other = fn(*args, ni=ni, seed=978, ctx=mctx)
+    finally:
+        mctx.close()
+    assert np.abs(one[1]).max() > 1e-2   # the learn left codes to compare
+    _assert_close([np.real(a) for a in two[:3]], [np.real(a) for a in one[:3]], 1e-10)
+    assert _rel(other[0], one[0]) > 1e-3   # the seed is what decides the draw
+
+
+def _host_comm():
+    import torch
+    import torch.distributed as dist
+
+    def host_comm(op, arr):
+        t = torch.from_numpy(arr)        # shares memory with the engine's staging buffer
+        if op == 0:
+            dist.all_reduce(t)
+        else:
+            dist.broadcast(t, src=0)
+    return host_comm
+
+
+def _odd_case():
+    from ccsc_code_iccv2017_amd import learners as E
+    c = _ODD
+    b = np.random.default_rng(47).standard_normal(c["sb"] + (c["n"],))
+    p = E.make_problem(E.L.CCSC_DPAR, b.shape, [c["psf"], c["psf"], c["K"]], 1.0, 1.0, 2, 0.0,
+                       "brief", ni=c["ni"], seed=4711)
+    return b, p
+
+
+def _hs_rng_problem(b, ks):
+    from ccsc_code_iccv2017_amd import learners as E
+    return E.make_problem(E.L.CCSC_HS23, b.shape, ks, 1.0, 0.2, 3, 0.0, "brief", seed=4713)
+
+
+def _rng_session_run(ctx, p, b, out, smooth_init=None):
+    """A session from the device draw: z and d at step 0, then the state after two steps."""
+    from ccsc_code_iccv2017_amd import learners as E
+    s = E.Session(ctx, p, b, None, None, smooth_init=smooth_init)
+    try:
+        d0, z0, _, _ = s.results(want_DZ=False)
+        s.step(2)
+        d, z, DZ, _ = s.results()
+    finally:
+        s.close()
+    np.savez(out, d0=d0, z0=z0, d=d, z=z, DZ=DZ)
+
+
+def _pair_worker(rank, world, port, out_dir):
+    """Every spawned two-rank case of this module in ONE process pair (a pair costs a
+    process start, a gloo rendezvous and a HIP initialisation each): the sharded 3D and 4D
+    sessions over the host transport, then the HS23 and dP sessions drawn on the device."""
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from ccsc_code_iccv2017_amd import learners as E
+    ctx = E.Context(0, rank, world, host_comm=_host_comm())
+    for name in ("L3", "L4"):
+        v, b, ks, init, (lr, lam, max_it, tol, vb), ni = _nd_case(name)
+        p = E.make_problem(E.L.CCSC_L3D if v == "L3" else E.L.CCSC_L4D, b.shape, ks, lr, lam,
+                           max_it, tol, vb, ni=ni, trace_objective=True)
+        b0, nb = E.shard(E.resolve(p), rank, world)
+        sl = slice(b0 * ni, (b0 + nb) * ni)
+        s = E.Session(ctx, p, b[..., sl], init["d"], init["z"][..., sl])
+        s.step(max_it)
+        d, z, DZ, obj = s.results(want_obj=True)
+        it = s.iterlog()
+        np.savez(os.path.join(out_dir, f"{name}_r{rank}.npz"), d=d, z=z, DZ=DZ, obj=obj,
+                 oz=it["trace"]["obj_z"], od=it["trace"]["obj_d"], b0=b0, nb=nb)
+        s.close()
+    b, sm, _, ks = _hs_case()
+    p = _hs_rng_problem(b, ks)
+    i0, nl = E.shard(E.resolve(p), rank, world)
+    _rng_session_run(ctx, p, b[..., i0:i0 + nl], os.path.join(out_dir, f"hsrng_r{rank}.npz"),
+                     smooth_init=sm[..., i0:i0 + nl])
+    b, p = _odd_case()
+    b0, nb = E.shard(E.resolve(p), rank, world)
+    _rng_session_run(ctx, p, b[..., b0:b0 + nb], os.path.join(out_dir, f"dprng_r{rank}.npz"))
+    ctx.close()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.fixture(scope="module")
+def pair_dir(tmp_path_factory):
+    import torch.multiprocessing as mp
+    out = tmp_path_factory.mktemp("pair")
+    mp.start_processes(_pair_worker, args=(2, _free_port(), str(out)), nprocs=2, join=True,
+                       start_method="spawn")
+    return out
+
+
+@pytest.mark.parametrize("name", ["L3", "L4"])
+def test_3d_4d_two_rank_sessions_equal_oracle(gpu_ctx, pair_dir, name):
+    """Session.step of the 3D / 4D learners over two ranks and the host transport (the
+    bench's path for C4 / C5): every rank returns block 1's filters, the final objective and
+    the global objective traces; the ranks' codes and reconstructions, concatenated, are the
+    oracle's."""
+    d_o, z_o, DZ_o, obj_o, tr_o = _nd_oracle(name)
+    parts = [np.load(pair_dir / f"{name}_r{r}.npz") for r in range(2)]
+    assert [int(q["nb"]) for q in parts] == [2, 1]
+    for q in parts:
+        assert _rel(q["d"], d_o) < 1e-7
+        assert abs(float(q["obj"]) - obj_o) <= 1e-9 * abs(obj_o)
+        np.testing.assert_allclose(q["oz"], np.array(tr_o["obj_z"]), rtol=1e-9)
+        np.testing.assert_allclose(q["od"], np.array(tr_o["obj_d"]), rtol=1e-9)
+    z = np.concatenate([q["z"] for q in parts], axis=-1)
+    DZ = np.concatenate([q["DZ"] for q in parts], axis=-1)
+    assert z.shape == z_o.shape and DZ.shape == DZ_o.shape
+    assert _rel(z, z_o) < 1e-7
+    assert _rel(DZ, DZ_o) < 1e-7
+
+
+def _check_rng_pair(tmp_path, gpu_ctx, pair_dir, tag, p, b, bar, split, smooth_init=None):
+    from rng_ref import FILTER_SEED_XOR, randn_ref
+    _rng_session_run(gpu_ctx, p, b, tmp_path / "one.npz", smooth_init=smooth_init)
+    one = np.load(tmp_path / "one.npz")
+    parts = [np.load(pair_dir / f"{tag}_r{r}.npz") for r in range(2)]
+    assert [q["z0"].shape[-1] for q in parts] == split
+    z0 = np.concatenate([q["z0"] for q in parts], axis=-1)
+    ref = randn_ref(z0.size, p.seed).reshape(z0.shape, order="F")
+    print(f"{tag}: step-0 max |z - randn_ref| = {np.abs(z0 - ref).max():.3e}; ranks hold "
+          f"{[q['z0'].shape[-1] for q in parts]} patches")
+    # the ranks' draws, side by side, ARE the one-rank draw and the reference stream
+    assert np.array_equal(z0, one["z0"]), (
+        f"sharded step-0 codes differ from the one-rank draw: max |diff| = "
+        f"{np.abs(z0 - one['z0']).max():.3e}, first differing patch "
+        f"{int(np.argmax(np.any(z0 != one['z0'], axis=tuple(range(z0.ndim - 1)))))}")
+    np.testing.assert_allclose(z0, ref, rtol=0, atol=1e-13)
+    for q in parts:
+        assert np.array_equal(q["d0"], one["d0"])
+        dref = randn_ref(one["d0"][..., 0, :].size if tag == "hsrng" else one["d0"].size,
+                         int(p.seed) ^ FILTER_SEED_XOR)
+        got = q["d0"][:, :, 0, :] if tag == "hsrng" else q["d0"]
+        np.testing.assert_allclose(got, dref.reshape(got.shape, order="F"), rtol=0, atol=1e-13)
+        np.testing.assert_allclose(q["d"], one["d"], rtol=0, atol=bar * np.abs(one["d"]).max())
+    for k in ("z", "DZ"):
+        got = np.concatenate([q[k] for q in parts], axis=-1)
+        np.testing.assert_allclose(got, one[k], rtol=0, atol=bar * np.abs(one[k]).max())
+
+
+def test_hs23_device_rng_two_ranks_equal_one_rank(tmp_path, gpu_ctx, pair_dir):
+    """The 2-3D learner with z0 = NULL over two ranks (images 3 + 2): rank 1 draws from
+    stream element 3 K P on, so the ranks' step-0 codes are bit for bit the one-rank draw and
+    within 1e-13 of tests/rng_ref.py (measured 1.8e-15); two steps later the runs still agree.
+    (With every rank drawing from element 0, as the engine did before this test, rank 1's
+    first images repeat rank 0's codes: max |diff| 4.9, first differing image 3.)"""
+    from ccsc_code_iccv2017_amd import learners as E
+    b, sm, _, ks = _hs_case()
+    p = E.resolve(_hs_rng_problem(b, ks))
+    _check_rng_pair(tmp_path, gpu_ctx, pair_dir, "hsrng", p, b, 1e-8, [3, 2], smooth_init=sm)
+
+
+def test_dp_device_rng_odd_offset_two_ranks_equal_one_rank(tmp_path, gpu_ctx, pair_dir):
+    """dP sessions with z0 = NULL over two ranks, rank 1 starting at the odd stream element
+    585 (the sine half of a pair first): step-0 codes bit for bit the one-rank draw and within
+    1e-13 of tests/rng_ref.py (measured 1.6e-15), and equal runs after two steps."""
+    from ccsc_code_iccv2017_amd import learners as E
+    b, p = _odd_case()
+    _check_rng_pair(tmp_path, gpu_ctx, pair_dir, "dprng", E.resolve(p), b, 1e-9, [1, 1])
