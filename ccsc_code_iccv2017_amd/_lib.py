@@ -115,6 +115,34 @@ class SolveLog(C.Structure):
                 ("diff", _dp), ("seconds", _dp)]
 
 
+# transform test hooks (ccsc_test_fft_plan and friends)
+FFT_SLICE2D, FFT_TTILE, FFT_LINE2D, FFT_LINE3D = 0, 1, 2, 3
+FFT_INST = {0: "all", 1: "rm42", 2: "fixed38", 3: "rm74"}
+FFT_MASK_GENERIC, FFT_MASK_PFA = 1 << 12, 1 << 13
+
+
+class FftDirPlan(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32),
+        ("npass", C.c_int32),
+        ("rad", C.c_int32 * 4),
+        ("twoff", C.c_int32 * 4),
+        ("pfa", C.c_int32),
+        ("lines", C.c_int32),
+        ("groups", C.c_int32),
+        ("ntw", C.c_int32),
+        ("lds_bytes", C.c_int32),
+        ("threads", C.c_int32),
+        ("cap", C.c_int32 * 4),
+        ("mask", C.c_int32),
+        ("tw_global", C.c_int32),
+    ]
+
+
+class FftPlan(C.Structure):
+    _fields_ = [("dir", FftDirPlan * 3), ("inst", C.c_int32), ("inst_mask", C.c_int32)]
+
+
 CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double)
 COMM_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int64)
 
@@ -167,6 +195,12 @@ SIGNATURES = {
                                       C.c_int32, C.c_char_p, C.c_size_t]),
     "ccsc_test_fft2d": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
                                     C.c_char_p, C.c_size_t]),
+    "ccsc_test_fft_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(FftPlan), C.c_char_p, C.c_size_t]),
+    "ccsc_test_gfft": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp,
+                                   _dp, _dp, C.c_char_p, C.c_size_t]),
+    "ccsc_test_tfft": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp,
+                                   _dp, _dp, C.c_char_p, C.c_size_t]),
 }
 
 _LIB = None

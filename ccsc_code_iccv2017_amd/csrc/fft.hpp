@@ -350,8 +350,10 @@ __device__ __forceinline__ void fft_pass(T* lds, int mode, const LineGeom& gin,
   lds_sync();
 }
 
-// Generic odd-prime radix-R Stockham pass (R not unrolled, e.g. 37 for the
-// 74-point grids):
+// Generic odd radix-R Stockham pass: any odd R without an unrolled butterfly.  The slice
+// planner (plan1d) feeds it primes >= 13 only (e.g. 37 for the 74-point grids); the line
+// planner (plan_line) prefers the fewest passes and feeds it any odd non-native factor,
+// composite included (105, 125 and 135 run as one pass of that radix, 60 as 4 x 15):
 //   out[(j-k)R + k + q Ns] = sum_r x[j + r nb] tw(r, k) w^(r q),   w = e^(SIGN 2 pi i/R).
 // The R-point DFT is evaluated in conjugate output pairs.  With twiddled inputs
 // x_r, s_r = x_r + x_{R-r}, d_r = x_r - x_{R-r} (r = 1..h, h = (R-1)/2) and

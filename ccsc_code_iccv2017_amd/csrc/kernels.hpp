@@ -192,6 +192,9 @@ hipError_t launch_to_ttiles_real(const T* src, T* dst, int Tn, int Yn, int Xh, i
 template <typename T>
 hipError_t launch_tfft(const cpx<T>* src, cpx<T>* dst, int64_t nslices, int Yn, int F2, int sign,
                        const cpx<T>* tw, const Grid2D& Gt, hipStream_t stream);
+// the k_tfft instantiation launch_tfft runs on tile Gt (values of CCSC_FFT_INST_*, ccsc.h)
+constexpr int kTfftAll = 0, kTfftRm42 = 1, kTfftFixed38 = 2;
+int tfft_instantiation(const Grid2D& Gt);
 template <typename T>
 hipError_t launch_plane_inv(int mode, const cpx<T>* src, T* dst, const T* yv, T* supp, T* norms,
                             int64_t nfirst, T scale, int r, int64_t nslices, int Tn,

@@ -560,6 +560,13 @@ hipError_t launch_to_ttiles_real(const T* src, T* dst, int Tn, int Yn, int Xh, i
   return hipGetLastError();
 }
 
+// the k_tfft instantiation of tile Gt: the compile-time 42 x 38 passes, the masked
+// {2, 3, 7} build where it holds the plan's butterflies, else every pass kind
+int tfft_instantiation(const Grid2D& Gt) {
+  if (!rm_fits(kRm42, Gt.py, Gt.Xh)) return kTfftAll;
+  return tline42_ok(Gt, 38) ? kTfftFixed38 : kTfftRm42;
+}
+
 template <typename T>
 hipError_t launch_tfft(const cpx<T>* src, cpx<T>* dst, int64_t nslices, int Yn, int F2, int sign,
                        const cpx<T>* tw, const Grid2D& Gt, hipStream_t stream) {
@@ -569,8 +576,8 @@ hipError_t launch_tfft(const cpx<T>* src, cpx<T>* dst, int64_t nslices, int Yn, 
     hipLaunchKernelGGL(kern, grid, dim3(kNT), tfft_smem_bytes(Gt, sizeof(T)), stream, src, dst,
                        Yn, F2, tw, Gt);
   };
-  const bool r42 = rm_fits(kRm42, Gt.py, Gt.Xh);
-  const bool f38 = r42 && tline42_ok(Gt, 38);
+  const int inst = tfft_instantiation(Gt);
+  const bool f38 = inst == kTfftFixed38, r42 = inst == kTfftRm42;
   if (sign < 0) {
     if (f38) go(k_tfft<T, -1, kRm42, 38>);
     else if (r42) go(k_tfft<T, -1, kRm42>);

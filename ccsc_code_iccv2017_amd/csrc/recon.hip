@@ -42,7 +42,8 @@ __device__ __forceinline__ T line_block_sum(T v, T* scratch) {
 // ---------------------------------------------------------------------------
 // Row pass: 2L rows (L row pairs) of one slice per workgroup.  LDS rows of RS T.
 // ---------------------------------------------------------------------------
-template <typename T, int MODE>
+// TWG: the twiddle table is read from global memory (RowGeom::twg), not staged into LDS
+template <typename T, int MODE, bool TWG = false>
 __device__ __forceinline__ void rows_body(const RowArgs<T>& a, const RowGeom& rg,
                                           const cpx<T>* __restrict__ tw, int64_t slice, T* lds) {
   Grid2D G = rg.G;
@@ -57,9 +58,14 @@ __device__ __forceinline__ void rows_body(const RowArgs<T>& a, const RowGeom& rg
   const int sl = (int)(slice - img * a.per_img);
   const int64_t rbase = (slice * rg.rows + row0) * (int64_t)X;     // real arrays
   const int64_t sbase = (slice * rg.rows + row0) * (int64_t)Xh;    // spectra
-  // twiddle tables in LDS (every pass reads them per butterfly)
-  cpx<T>* s_tw = reinterpret_cast<cpx<T>*>(lds + rows_tw_off(rg));
-  batched_loop<4, kLineNT>(rg.ntw, [&](int i) { return tw[i]; }, [&](int i, cpx<T> v) { s_tw[i] = v; });
+  // twiddle tables in LDS (every pass reads them per butterfly) unless the plan left them
+  // in global memory
+  const cpx<T>* s_tw = tw;
+  if constexpr (!TWG) {
+    cpx<T>* l_tw = reinterpret_cast<cpx<T>*>(lds + rows_tw_off(rg));
+    batched_loop<4, kLineNT>(rg.ntw, [&](int i) { return tw[i]; }, [&](int i, cpx<T> v) { l_tw[i] = v; });
+    s_tw = l_tw;
+  }
 
   // ---- load (batched: every load of a batch in flight before the first LDS store) ----
   if (MODE == kRowFwd) {
@@ -216,31 +222,31 @@ __device__ __forceinline__ void rows_body(const RowArgs<T>& a, const RowGeom& rg
   }
 }
 
-template <typename T, int MODE>
+template <typename T, int MODE, bool TWG = false>
 __global__ __launch_bounds__(kLineNT) void k_rows(RowArgs<T> a, RowGeom rg,
                                               const cpx<T>* __restrict__ tw) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
-  rows_body<T, MODE>(a, rg, tw, (int64_t)blockIdx.x, reinterpret_cast<T*>(smem_raw));
+  rows_body<T, MODE, TWG>(a, rg, tw, (int64_t)blockIdx.x, reinterpret_cast<T*>(smem_raw));
 }
 
 // One launch for both slice sets of an iteration: workgroups [0, nz) run the code
 // slices (MZ = kRowIterZ or kRowFinalZ) with args a, the rest the data slices
 // (kRowIterX) with args b -- the single-image data launch alone would leave the GPU
 // nearly idle for its whole latency.
-template <typename T, int MZ>
+template <typename T, int MZ, bool TWG = false>
 __global__ __launch_bounds__(kLineNT) void k_rows_pair(RowArgs<T> a, RowArgs<T> b, int64_t nz,
                                                    RowGeom rg, const cpx<T>* __restrict__ tw) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* lds = reinterpret_cast<T*>(smem_raw);
   const int64_t s = blockIdx.x;
-  if (s < nz) rows_body<T, MZ>(a, rg, tw, s, lds);
-  else rows_body<T, kRowIterX>(b, rg, tw, s - nz, lds);
+  if (s < nz) rows_body<T, MZ, TWG>(a, rg, tw, s, lds);
+  else rows_body<T, kRowIterX, TWG>(b, rg, tw, s - nz, lds);
 }
 
 // ---------------------------------------------------------------------------
 // Column pass: TC consecutive x' columns of one line set, LDS [e][c] complex.
 // ---------------------------------------------------------------------------
-template <typename T, int SIGN>
+template <typename T, int SIGN, bool TWG = false>
 __global__ __launch_bounds__(kLineNT) void k_cols(cpx<T>* __restrict__ S, cpx<T>* __restrict__ S2,
                                               int64_t n1, ColGeom cg,
                                               const cpx<T>* __restrict__ tw, int64_t ntot) {
@@ -262,8 +268,12 @@ __global__ __launch_bounds__(kLineNT) void k_cols(cpx<T>* __restrict__ S, cpx<T>
   const int c0 = tile * TC;
   const int nc = min(TC, cg.Xh - c0);
   cpx<T>* base = S + (o % cg.ninner) * cg.sin + (o / cg.ninner) * cg.sout + c0;
-  cpx<T>* s_tw = reinterpret_cast<cpx<T>*>(lds + (size_t)2 * n * TC);
-  batched_loop<4, kLineNT>(cg.ntw, [&](int i) { return tw[i]; }, [&](int i, cpx<T> v) { s_tw[i] = v; });
+  const cpx<T>* s_tw = tw;
+  if constexpr (!TWG) {
+    cpx<T>* l_tw = reinterpret_cast<cpx<T>*>(lds + (size_t)2 * n * TC);
+    batched_loop<4, kLineNT>(cg.ntw, [&](int i) { return tw[i]; }, [&](int i, cpx<T> v) { l_tw[i] = v; });
+    s_tw = l_tw;
+  }
   // the line set's columns, four loads in flight per thread before their LDS stores
   batched_loop<4, kLineNT>(
       n * TC,
@@ -429,10 +439,10 @@ __global__ __launch_bounds__(256) void k_reduce_parts(const T* __restrict__ part
 // launchers
 // ---------------------------------------------------------------------------
 size_t rows_smem_bytes(const RowGeom& rg, size_t tsize) {
-  return (rows_tw_off(rg) + 2 * (size_t)rg.ntw) * tsize;
+  return (rows_tw_off(rg) + (rg.twg ? 0 : 2 * (size_t)rg.ntw)) * tsize;
 }
 size_t cols_smem_bytes(const ColGeom& cg, size_t tsize) {
-  return ((size_t)cg.n * cg.TC * 2 + 2 * (size_t)cg.ntw) * tsize;
+  return ((size_t)cg.n * cg.TC * 2 + (cg.twg ? 0 : 2 * (size_t)cg.ntw)) * tsize;
 }
 
 template <typename T>
@@ -441,6 +451,17 @@ hipError_t launch_rows(int mode, const RowArgs<T>& a, int64_t nslices, const Row
   if (nslices <= 0) return hipSuccess;
   const dim3 grid((unsigned)nslices, (unsigned)rg.groups);
   const size_t sm = rows_smem_bytes(rg, sizeof(T));
+  if (rg.twg) {
+    switch (mode) {
+      case kRowFwd: hipLaunchKernelGGL((k_rows<T, kRowFwd, true>), grid, dim3(kLineNT), sm, st, a, rg, tw); break;
+      case kRowIterZ: hipLaunchKernelGGL((k_rows<T, kRowIterZ, true>), grid, dim3(kLineNT), sm, st, a, rg, tw); break;
+      case kRowIterX: hipLaunchKernelGGL((k_rows<T, kRowIterX, true>), grid, dim3(kLineNT), sm, st, a, rg, tw); break;
+      case kRowFinalZ: hipLaunchKernelGGL((k_rows<T, kRowFinalZ, true>), grid, dim3(kLineNT), sm, st, a, rg, tw); break;
+      case kRowRes: hipLaunchKernelGGL((k_rows<T, kRowRes, true>), grid, dim3(kLineNT), sm, st, a, rg, tw); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   switch (mode) {
     case kRowFwd: hipLaunchKernelGGL((k_rows<T, kRowFwd>), grid, dim3(kLineNT), sm, st, a, rg, tw); break;
     case kRowIterZ: hipLaunchKernelGGL((k_rows<T, kRowIterZ>), grid, dim3(kLineNT), sm, st, a, rg, tw); break;
@@ -460,7 +481,11 @@ hipError_t launch_cols(cpx<T>* S, int sign, int64_t nouter, const ColGeom& cg, c
   if (ntot >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
   const dim3 grid((unsigned)(((ntot + 7) / 8) * 8));
   const size_t sm = cols_smem_bytes(cg, sizeof(T));
-  if (sign < 0)
+  if (cg.twg && sign < 0)
+    hipLaunchKernelGGL((k_cols<T, -1, true>), grid, dim3(kLineNT), sm, st, S, S2, nouter, cg, tw, ntot);
+  else if (cg.twg)
+    hipLaunchKernelGGL((k_cols<T, +1, true>), grid, dim3(kLineNT), sm, st, S, S2, nouter, cg, tw, ntot);
+  else if (sign < 0)
     hipLaunchKernelGGL((k_cols<T, -1>), grid, dim3(kLineNT), sm, st, S, S2, nouter, cg, tw, ntot);
   else
     hipLaunchKernelGGL((k_cols<T, +1>), grid, dim3(kLineNT), sm, st, S, S2, nouter, cg, tw, ntot);
@@ -473,7 +498,11 @@ hipError_t launch_rows_pair(int code_mode, const RowArgs<T>& a, int64_t nz, cons
   if (nz + nx <= 0) return hipSuccess;
   const dim3 grid((unsigned)(nz + nx), (unsigned)rg.groups);
   const size_t sm = rows_smem_bytes(rg, sizeof(T));
-  if (code_mode == kRowIterZ)
+  if (rg.twg && code_mode == kRowIterZ)
+    hipLaunchKernelGGL((k_rows_pair<T, kRowIterZ, true>), grid, dim3(kLineNT), sm, st, a, b, nz, rg, tw);
+  else if (rg.twg && code_mode == kRowFinalZ)
+    hipLaunchKernelGGL((k_rows_pair<T, kRowFinalZ, true>), grid, dim3(kLineNT), sm, st, a, b, nz, rg, tw);
+  else if (code_mode == kRowIterZ)
     hipLaunchKernelGGL((k_rows_pair<T, kRowIterZ>), grid, dim3(kLineNT), sm, st, a, b, nz, rg, tw);
   else if (code_mode == kRowFinalZ)
     hipLaunchKernelGGL((k_rows_pair<T, kRowFinalZ>), grid, dim3(kLineNT), sm, st, a, b, nz, rg, tw);

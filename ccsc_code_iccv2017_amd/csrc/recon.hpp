@@ -27,6 +27,8 @@ struct RowGeom {
   int L;
   int groups;
   int ntw;     // twiddle table length (complex), staged into LDS
+  int twg;     // 1: the table does not fit the workgroup's LDS budget next to the rows and is
+               // read from global memory instead (long lines only, see plan_rows)
 };
 
 // Column-pass geometry: lines of length n with element stride es (complex units),
@@ -36,6 +38,7 @@ struct ColGeom {
   Plan1D p;
   int n, TC, Xh, xtiles, ninner;
   int ntw;     // twiddle table length (complex), staged into LDS
+  int twg;     // 1: the table stays in global memory (as RowGeom::twg)
   int64_t es, sin, sout;
 };
 

@@ -126,14 +126,19 @@ static bool plan_rows(int X, int rows, RowGeom& rg) {
   G.RS = 2 * G.Xh;
   while (G.RS % 16 != 6) G.RS += 2;   // column-pair lines off the same LDS banks (engine.cpp)
   rg.rows = rows;
-  for (int L = (rows + 1) / 2; L >= 1; --L) {
-    rg.L = L;
-    if (!plan_line(X, L, G.px)) continue;
-    rg.ntw = twiddle_count(G.px);
-    if (rows_smem_bytes(rg, sizeof(double)) > line_lds()) continue;
-    rg.groups = (rows + 2 * L - 1) / (2 * L);
-    return true;
-  }
+  // the twiddle table next to the rows in LDS; lines too long for both (a 2048-point table
+  // and one row pair, or the n roots of a one-pass generic plan past n = 853, are more than
+  // the budget) keep the table in global memory (twg)
+  for (int twg = 0; twg < 2; ++twg)
+    for (int L = (rows + 1) / 2; L >= 1; --L) {
+      rg.L = L;
+      rg.twg = twg;
+      if (!plan_line(X, L, G.px)) continue;
+      rg.ntw = twiddle_count(G.px);
+      if (rows_smem_bytes(rg, sizeof(double)) > line_lds()) continue;
+      rg.groups = (rows + 2 * L - 1) / (2 * L);
+      return true;
+    }
   return false;
 }
 
@@ -141,14 +146,16 @@ static bool plan_cols(int n, int Xh, ColGeom& cg) {
   cg = ColGeom{};
   cg.n = n;
   cg.Xh = Xh;
-  for (int TC = std::min(32, Xh); TC >= 1; --TC) {
-    cg.TC = TC;
-    if (!plan_line(n, TC, cg.p)) continue;
-    cg.ntw = twiddle_count(cg.p);
-    if (cols_smem_bytes(cg, sizeof(double)) > line_lds()) continue;
-    cg.xtiles = (Xh + TC - 1) / TC;
-    return true;
-  }
+  for (int twg = 0; twg < 2; ++twg)   // (as plan_rows)
+    for (int TC = std::min(32, Xh); TC >= 1; --TC) {
+      cg.TC = TC;
+      cg.twg = twg;
+      if (!plan_line(n, TC, cg.p)) continue;
+      cg.ntw = twiddle_count(cg.p);
+      if (cols_smem_bytes(cg, sizeof(double)) > line_lds()) continue;
+      cg.xtiles = (Xh + TC - 1) / TC;
+      return true;
+    }
   return false;
 }
 

@@ -594,3 +594,60 @@ def fft2d_test(ctx: Context, slices):
                                     len(eb)), eb)
     h = hs.view(np.complex128).reshape(cnt, Y, Xh)          # [slice][y][x']
     return np.transpose(h, (2, 1, 0)), rt                     # [x', y, slice]
+
+
+def fft_plan(family, X, Y=1, T=1):
+    """Host only: the transform plan the sessions would run (ccsc_test_fft_plan).  ``family``
+    is L.FFT_SLICE2D (grid X x Y), L.FFT_TTILE (X = Xh lines, T = Tn), L.FFT_LINE2D or
+    L.FFT_LINE3D.  Returns {'x' | 'y' | 't': direction dict, 'inst': name, 'inst_mask': int}
+    with the directions the family has; raises CCSCError (CCSC_E_UNSUPPORTED) with the
+    planner's message when there is no plan."""
+    out = L.FftPlan()
+    eb = L.errbuf()
+    L.check(L.lib().ccsc_test_fft_plan(int(family), int(X), int(Y), int(T), out, eb, len(eb)), eb)
+    res = {"inst": L.FFT_INST[out.inst], "inst_mask": int(out.inst_mask)}
+    for name, d in zip("xyt", out.dir):
+        if d.n == 0:
+            continue
+        np_ = int(d.npass)
+        res[name] = {"n": int(d.n), "npass": np_, "rad": list(d.rad[:np_]),
+                     "twoff": list(d.twoff[:np_]), "pfa": bool(d.pfa), "lines": int(d.lines),
+                     "groups": int(d.groups), "ntw": int(d.ntw), "lds_bytes": int(d.lds_bytes),
+                     "threads": int(d.threads), "cap": list(d.cap[:np_]), "mask": int(d.mask),
+                     "tw_global": bool(d.tw_global)}
+    return res
+
+
+def gfft_test(ctx: Context, vols):
+    """Kernel-level check of the global line passes: [X, Y, count] (2D plan) or
+    [X, Y, T, count] real slices -> (half spectra [x', y, (t,) slice], round trip)."""
+    a = np.asfortranarray(np.asarray(vols, dtype=np.float64))
+    if a.ndim == 3:
+        X, Y, cnt = a.shape
+        T = 1
+    else:
+        X, Y, T, cnt = a.shape
+    Xh = X // 2 + 1
+    hs = np.zeros(2 * Xh * Y * T * cnt)
+    rt = np.zeros_like(a, order="F")
+    eb = L.errbuf()
+    L.check(L.lib().ccsc_test_gfft(ctx.ptr, X, Y, T, cnt, L.dptr(a), L.dptr(hs), L.dptr(rt), eb,
+                                   len(eb)), eb)
+    h = hs.view(np.complex128).reshape(cnt, T, Y, Xh)        # [slice][t][y][x']
+    h = np.transpose(h, (3, 2, 1, 0))
+    return (h[:, :, 0, :] if a.ndim == 3 else h), rt
+
+
+def tfft_test(ctx: Context, tiles):
+    """Kernel-level check of the 3D learner's t-tile transform: complex [Xh, Yn, Tn, count]
+    (x' fastest) -> (forward transform along t, forward then inverse).  The inverse is
+    unnormalised: the round trip returns Tn times the input."""
+    a = np.asfortranarray(np.asarray(tiles, dtype=np.complex128))
+    Xh, Yn, Tn, cnt = a.shape
+    out = np.zeros_like(a, order="F")
+    rt = np.zeros_like(a, order="F")
+    eb = L.errbuf()
+    f64 = lambda z: z.ctypes.data_as(L._dp)      # (re, im) pairs
+    L.check(L.lib().ccsc_test_tfft(ctx.ptr, Tn, Xh, Yn, cnt, f64(a), f64(out), f64(rt), eb,
+                                   len(eb)), eb)
+    return out, rt

@@ -355,6 +355,76 @@ int32_t ccsc_local_cn_dev(ccsc_ctx* ctx, const double* in, double* out, int64_t 
 int32_t ccsc_test_fft2d(ccsc_ctx* ctx, int32_t X, int32_t Y, int32_t count, const double* in,
                         double* out_halfspec, double* roundtrip, char* err, size_t errlen);
 
+/* The hooks below are additive test entry points: they add no kernel and change no
+ * structure or constant of ABI 7, so CCSC_ABI_VERSION stays (it moves when an existing
+ * caller would have to change).  Every hook validates its arguments and plans before
+ * it launches anything: a geometry the planner rejects returns CCSC_E_UNSUPPORTED with
+ * the planner's message and launches nothing.
+ *
+ * Transform families (SLICE2D: the LDS slice R2C / C2R of the learners; TTILE: the 3D
+ * learner's t-direction tile; LINE2D / LINE3D: the global row / column line passes). */
+#define CCSC_FFT_SLICE2D 0
+#define CCSC_FFT_TTILE 1
+#define CCSC_FFT_LINE2D 2
+#define CCSC_FFT_LINE3D 3
+/* kernel instantiation a plan runs on: every pass kind; the {2, 3, 7} build of the t
+ * tiles; its compile-time 42 x 38 form; the {2, prime-factor 37} build of the slices */
+#define CCSC_FFT_INST_ALL 0
+#define CCSC_FFT_INST_RM42 1
+#define CCSC_FFT_INST_FIXED38 2
+#define CCSC_FFT_INST_RM74 3
+
+/* Plan of one transform direction.  n == 0: the family has no such direction. */
+typedef struct ccsc_fft_dir_plan {
+  int32_t n;         /* line length                                                      */
+  int32_t npass;     /* passes, rad[0..npass-1] in execution order                       */
+  int32_t rad[4];
+  int32_t twoff[4];  /* offset (complex) of pass s's table in the direction's twiddle
+                        buffer: (R-1) Ns twiddles, then the R roots of a non-native R    */
+  int32_t pfa;       /* 1: pass 1 is the prime-factor pass (74 = 2 * 37)                 */
+  int32_t lines;     /* lines per workgroup: Yp/2 (slice x), Xh (slice y, t tile), L row
+                        pairs (line rows), TC columns (line columns)                     */
+  int32_t groups;    /* workgroups per slice (slice, t tile: 1; rows: groups; columns:
+                        xtiles per line set)                                             */
+  int32_t ntw;       /* length (complex) of the twiddle buffer the direction reads; the
+                        two directions of a slice share one (x tables, then y tables)    */
+  int32_t lds_bytes; /* dynamic LDS of a workgroup (slice: the largest any slice kernel
+                        asks for, the figure the planner bounds)                         */
+  int32_t threads;   /* threads per workgroup                                            */
+  int32_t cap[4];    /* per pass, what the instantiation holds: butterflies (native
+                        radix), tasks of 3 conjugate output pairs (generic radix), task
+                        slots (prime-factor pass)                                        */
+  int32_t mask;      /* pass kinds the plan needs: bit R per native radix R, bit 12 the
+                        generic pass, bit 13 the prime-factor pass                       */
+  int32_t tw_global; /* 1: the twiddle buffer is read from global memory, not staged into
+                        LDS (long lines of the line families), lds_bytes excludes it     */
+} ccsc_fft_dir_plan;
+
+typedef struct ccsc_fft_plan {
+  ccsc_fft_dir_plan dir[3]; /* x, y, t (TTILE: t only)                                   */
+  int32_t inst;             /* CCSC_FFT_INST_*: SLICE2D and TTILE; lines are always ALL  */
+  int32_t inst_mask;        /* pass kinds that instantiation compiles                    */
+} ccsc_fft_plan;
+
+/* Host only (no context, no GPU): the plan the sessions would run, from the planners
+ * they call.  SLICE2D: grid X x Y (T ignored); TTILE: X carries Xh (lines), T carries
+ * Tn (Y ignored); LINE2D: X x Y; LINE3D: X x Y x T. */
+int32_t ccsc_test_fft_plan(int32_t family, int32_t X, int32_t Y, int32_t T, ccsc_fft_plan* out,
+                           char* err, size_t errlen);
+/* Global line passes on `count` real slices [X, Y, T] (T == 1: the 2D plan): row R2C,
+ * then the y (and t) column passes -> out_halfspec [count][T][Y][X/2+1] (re,im); then
+ * the inverse column passes and the row C2R scaled by 1/(X Y T) -> roundtrip (same shape
+ * as in).  Either output may be NULL. */
+int32_t ccsc_test_gfft(ccsc_ctx* ctx, int32_t X, int32_t Y, int32_t T, int32_t count,
+                       const double* in, double* out_halfspec, double* roundtrip, char* err,
+                       size_t errlen);
+/* t-tile transform of `count` complex slices [count][Tn][Yn * Xh] (re,im), one
+ * workgroup per (slice, y): forward along t -> out; then the inverse of that result ->
+ * roundtrip.  The inverse is NOT normalised: roundtrip = Tn * in.  Either may be NULL. */
+int32_t ccsc_test_tfft(ccsc_ctx* ctx, int32_t Tn, int32_t Xh, int32_t Yn, int32_t count,
+                       const double* in, double* out, double* roundtrip, char* err,
+                       size_t errlen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,17 @@ def test_fft2d_r2c_c2r(gpu_ctx, X, Y):
     assert np.abs(rt - a).max() < 1e-12
 
 
+def _unplanned(family, X, Y=1, T=1):
+    """True when the planner of `family` rejects the geometry (ccsc_test_fft_plan)."""
+    from ccsc_code_iccv2017_amd import learners as E
+    try:
+        E.fft_plan(family, X, Y, T)
+    except E.L.CCSCError as e:
+        assert e.code == E.L.CCSC_E_UNSUPPORTED
+        return True
+    return False
+
+
 def _case(variant, sb, psf, K, n, ni, seed):
     rng = np.random.default_rng(seed)
     b = rng.standard_normal((sb[0], sb[1], n))
@@ -72,9 +83,15 @@ def _case(variant, sb, psf, K, n, ni, seed):
                                            # K > 400: the reference's Woodbury form on the
                                            # ni x ni factor (wbig.hip), ni = 2 and 12
                                            ((6, 6), 5, 420, 4, 2),
-                                           ((6, 6), 5, 450, 24, 12)])
+                                           ((6, 6), 5, 450, 24, 12),
+                                           # the small-grid fallback: 54 = 2 3^3 has no slice
+                                           # plan, so a grid that fits the LDS runs on the
+                                           # global line passes
+                                           ((44, 44), 11, 3, 4, 2)])
 def test_learn_2d_matches_oracle(gpu_ctx, variant, sb, psf, K, n, ni):
     from ccsc_code_iccv2017_amd import learners as E
+    if sb == (44, 44):
+        assert _unplanned(E.L.FFT_SLICE2D, 54, 54)
     b, d0, z0 = _case(variant, sb, psf, K, n, ni, seed=7)
     ks = [psf, psf, K]
     init = {"d": d0, "z": z0}
@@ -375,11 +392,18 @@ def test_learn_4d_grid_past_lds_matches_oracle(gpu_ctx, tol):
 @pytest.mark.parametrize("sb,psf,K,n,tol", [((8, 9, 7), 3, 3, 4, 0.0), ((10, 10, 6), 5, 4, 9, 0.0),
                                             ((10, 10, 6), 5, 4, 9, 2e-2),
                                             ((20, 20, 12), 11, 8, 4, 0.0),   # Woodbury
-                                            ((64, 64, 32), 11, 2, 1, 0.0)])   # C4 grid 74x74x42
+                                            ((64, 64, 32), 11, 2, 1, 0.0),   # C4 grid 74x74x42
+                                            # 10 x 11 planes fit the LDS, T = 54 is the shortest
+                                            # length without a t-tile plan: the line passes
+                                            ((8, 9, 52), 3, 3, 4, 0.0)])
 def test_learn_3d_matches_oracle(gpu_ctx, sb, psf, K, n, tol):
     """3D learner (L3:1-230): plane R2C/C2R + t-direction FFT, Sherman-Morrison z-solve,
     psf^3 support projection; odd/even and ragged grid extents."""
     from ccsc_code_iccv2017_amd import learners as E
+    if sb == (8, 9, 52):
+        assert not _unplanned(E.L.FFT_SLICE2D, 10, 11)
+        assert _unplanned(E.L.FFT_TTILE, 6, 1, 54)
+        assert not any(_unplanned(E.L.FFT_TTILE, 6, 1, t) for t in range(2, 54))
     rng = np.random.default_rng(21)
     r = psf // 2
     g = tuple(s + 2 * r for s in sb)
