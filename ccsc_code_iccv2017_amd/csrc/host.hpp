@@ -4,6 +4,7 @@
 
 #include "../../include/ccsc.h"
 #include "kernels.hpp"
+#include "plan.hpp"
 
 #include <rccl/rccl.h>
 
@@ -17,11 +18,6 @@
 #include <vector>
 
 namespace ccsc {
-
-struct Err : std::runtime_error {
-  int code;
-  Err(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 
 #define HIPCHK(x)                                                                         \
   do {                                                                                    \
@@ -81,6 +77,55 @@ struct DevBuf {
     bytes = 0;
   }
   template <typename X> X* as() const { return reinterpret_cast<X*>(p); }
+};
+
+// a twiddle table onto the device (into b, allocated here unless a memory plan already did)
+inline const cpx<double>* upload_twiddles(DevBuf& b, const std::vector<cpx<double>>& t) {
+  if (!b.p) b.alloc(t.size() * sizeof(cpx<double>));
+  HIPCHK(hipMemcpy(b.p, t.data(), t.size() * sizeof(cpx<double>), hipMemcpyHostToDevice));
+  return b.as<cpx<double>>();
+}
+
+// The global line passes of one grid (recon.hip) on a stream: their twiddle tables on the
+// device and the unnormalised transforms of whole slices, real [count][t][y][x] <-> half
+// spectra [count][t][y][x'] (rows, y-lines per plane, t-lines over the Y rows of a slice).
+struct LinePass {
+  LinePlan lp;
+  hipStream_t st = nullptr;
+  const cpx<double>*twr = nullptr, *twy = nullptr, *twt = nullptr;
+
+  // uploads the tables into r, y (and *t, for a plan with t-lines)
+  void setup(const LinePlan& plan, hipStream_t stream, DevBuf& r, DevBuf& y,
+             DevBuf* t = nullptr) {
+    lp = plan;
+    st = stream;
+    twr = upload_twiddles(r, make_twiddles(lp.rg.ntw, {&lp.rg.G.px}));
+    twy = upload_twiddles(y, make_twiddles(lp.cy.ntw, {&lp.cy.p}));
+    if (lp.with_t) twt = upload_twiddles(*t, make_twiddles(lp.ct.ntw, {&lp.ct.p}));
+  }
+  void r2c(const double* src, cpx<double>* dst, int64_t count) const {
+    RowArgs<double> a{};
+    a.S = dst;
+    a.src = src;
+    a.per_img = 1;
+    HIPCHK(launch_rows<double>(kRowFwd, a, count, lp.rg, twr, st));
+    HIPCHK(launch_cols<double>(dst, -1, count * lp.Tn, lp.cy, twy, st));
+    if (lp.with_t) HIPCHK(launch_cols<double>(dst, -1, count * lp.Y, lp.ct, twt, st));
+  }
+  // the inverse column passes alone, in place (c2r's first half; ccsc_test_gfft's inverse)
+  void inv_cols(cpx<double>* src, int64_t count) const {
+    if (lp.with_t) HIPCHK(launch_cols<double>(src, +1, count * lp.Y, lp.ct, twt, st));
+    HIPCHK(launch_cols<double>(src, +1, count * lp.Tn, lp.cy, twy, st));
+  }
+  // src is overwritten by the inverse column passes
+  void c2r(cpx<double>* src, double* dst, int64_t count) const {
+    inv_cols(src, count);
+    RowArgs<double> a{};
+    a.S = src;
+    a.Z = dst;
+    a.per_img = 1;
+    HIPCHK(launch_rows<double>(kRowFinalZ, a, count, lp.rg, twr, st));
+  }
 };
 
 }  // namespace ccsc

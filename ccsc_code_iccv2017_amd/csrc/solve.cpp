@@ -19,186 +19,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <limits>
 
 namespace ccsc {
-
-static const int kNativeRad[] = {11, 10, 8, 7, 5, 4, 3, 2};   // fft_pass_dispatch
-
-static bool native_rad(int R) {
-  for (int r : kNativeRad)
-    if (r == R) return true;
-  return false;
-}
-
-static int64_t gen_tasks(int n, int nlines, int R) {
-  return (int64_t)nlines * (n / R) * (((R - 1) / 2 + kGenericQP - 1) / kGenericQP);
-}
-
-// Line plan of length n for `nlines` lines per workgroup: fewest passes (<= kPlanSlots),
-// then fewest generic passes.  Native radices need (n/R) * nlines butterflies within
-// the register budget; any other odd factor runs as a generic pass (fft_pass_generic,
-// one task per thread).  Lengths with an even factor outside {2,4,8,10} beyond the
-// native set, e.g. 2^5 * 3 = 96 = 8 * 4 * 3, still plan.
-static bool plan_line(int n, int nlines, Plan1D& out) {
-  if (n == 1) {
-    out = Plan1D{};
-    out.n = 1;
-    return true;
-  }
-  Plan1D best{};
-  int best_np = 99, best_ng = 99;
-  std::vector<int> cur;
-  std::function<void(int, int)> dfs = [&](int rem, int ng) {
-    if (rem == 1) {
-      const int np = (int)cur.size();
-      if (np < best_np || (np == best_np && ng < best_ng)) {
-        best_np = np;
-        best_ng = ng;
-        best = Plan1D{};
-        best.n = n;
-        best.npass = np;
-        for (int i = 0; i < np; ++i) best.rad[i] = cur[i];
-      }
-      return;
-    }
-    if ((int)cur.size() >= kPlanSlots || (int)cur.size() + 1 > best_np) return;
-    for (int R : kNativeRad) {
-      if (rem % R) continue;
-      if ((int64_t)(n / R) * nlines > (int64_t)maxb_for_radix(R) * kLineBS * kLineNT) continue;
-      cur.push_back(R);
-      dfs(rem / R, ng);
-      cur.pop_back();
-    }
-    for (int R = 3; R <= rem; R += 2) {
-      if (rem % R || native_rad(R)) continue;
-      if (gen_tasks(n, nlines, R) > (int64_t)kLineGT * kLineNT) continue;
-      cur.push_back(R);
-      dfs(rem / R, ng + 1);
-      cur.pop_back();
-    }
-  };
-  dfs(n, 0);
-  if (best_np == 99) return false;
-  out = best;
-  return true;
-}
-
-// twiddle tables of one plan, appended to t (offsets into t in p.twoff)
-static void add_twiddles(Plan1D& p, std::vector<cpx<double>>& t) {
-  const long double pi = 3.141592653589793238462643383279502884L;
-  int Ns = 1;
-  for (int s = 0; s < p.npass; ++s) {
-    const int R = p.rad[s];
-    p.twoff[s] = (int)t.size();
-    for (int r = 1; r < R; ++r)
-      for (int k = 0; k < Ns; ++k) {
-        const long double a = -2.0L * pi * (long double)(r * k) / (long double)(Ns * R);
-        t.push_back({(double)cosl(a), (double)sinl(a)});
-      }
-    if (!native_rad(R))
-      for (int m = 0; m < R; ++m) {
-        const long double a = -2.0L * pi * (long double)m / (long double)R;
-        t.push_back({(double)cosl(a), (double)sinl(a)});
-      }
-    Ns *= R;
-  }
-}
-
-// LDS budget of one line-kernel workgroup (four or more per CU)
-static size_t line_lds() { return (size_t)40 * 1024; }
-
-static int twiddle_count(const Plan1D& p) {
-  int n = 0, Ns = 1;
-  for (int s = 0; s < p.npass; ++s) {
-    n += (p.rad[s] - 1) * Ns + (native_rad(p.rad[s]) ? 0 : p.rad[s]);
-    Ns *= p.rad[s];
-  }
-  return std::max(n, 1);
-}
-
-static bool plan_rows(int X, int rows, RowGeom& rg) {
-  rg = RowGeom{};
-  Grid2D& G = rg.G;
-  G.X = X;
-  G.Xh = X / 2 + 1;
-  G.RS = 2 * G.Xh;
-  while (G.RS % 16 != 6) G.RS += 2;   // column-pair lines off the same LDS banks (engine.cpp)
-  rg.rows = rows;
-  // the twiddle table next to the rows in LDS; lines too long for both (a 2048-point table
-  // and one row pair, or the n roots of a one-pass generic plan past n = 853, are more than
-  // the budget) keep the table in global memory (twg)
-  for (int twg = 0; twg < 2; ++twg)
-    for (int L = (rows + 1) / 2; L >= 1; --L) {
-      rg.L = L;
-      rg.twg = twg;
-      if (!plan_line(X, L, G.px)) continue;
-      rg.ntw = twiddle_count(G.px);
-      if (rows_smem_bytes(rg, sizeof(double)) > line_lds()) continue;
-      rg.groups = (rows + 2 * L - 1) / (2 * L);
-      return true;
-    }
-  return false;
-}
-
-static bool plan_cols(int n, int Xh, ColGeom& cg) {
-  cg = ColGeom{};
-  cg.n = n;
-  cg.Xh = Xh;
-  for (int twg = 0; twg < 2; ++twg)   // (as plan_rows)
-    for (int TC = std::min(32, Xh); TC >= 1; --TC) {
-      cg.TC = TC;
-      cg.twg = twg;
-      if (!plan_line(n, TC, cg.p)) continue;
-      cg.ntw = twiddle_count(cg.p);
-      if (cols_smem_bytes(cg, sizeof(double)) > line_lds()) continue;
-      cg.xtiles = (Xh + TC - 1) / TC;
-      return true;
-    }
-  return false;
-}
-
-bool gfft_plan(int X, int Y, RowGeom& rg, ColGeom& cy, std::vector<cpx<double>>& tw_rows,
-               std::vector<cpx<double>>& tw_cy) {
-  if (!plan_rows(X, Y, rg) || !plan_cols(Y, X / 2 + 1, cy)) return false;
-  const int Xh = X / 2 + 1;
-  cy.es = Xh;
-  cy.ninner = 1;
-  cy.sin = 0;
-  cy.sout = (int64_t)Xh * Y;
-  tw_rows.clear();
-  tw_cy.clear();
-  add_twiddles(rg.G.px, tw_rows);
-  add_twiddles(cy.p, tw_cy);
-  return true;
-}
-
-// 3D grids X x Y x T (the 3D learner's slices past one CU's LDS or past the t-tile
-// kernels): rows over the Y T rows of a slice, y-lines per plane, t-lines over the Y rows
-// of a slice (the video solver's passes, resolve_solve)
-bool gfft_plan3(int X, int Y, int Tn, RowGeom& rg, ColGeom& cy, ColGeom& ct,
-                std::vector<cpx<double>>& tw_rows, std::vector<cpx<double>>& tw_cy,
-                std::vector<cpx<double>>& tw_ct) {
-  if (!plan_rows(X, Y * Tn, rg) || !plan_cols(Y, X / 2 + 1, cy) || !plan_cols(Tn, X / 2 + 1, ct))
-    return false;
-  const int Xh = X / 2 + 1;
-  cy.es = Xh;
-  cy.ninner = 1;
-  cy.sin = 0;
-  cy.sout = (int64_t)Xh * Y;
-  ct.es = (int64_t)Xh * Y;
-  ct.ninner = Y;
-  ct.sin = Xh;
-  ct.sout = (int64_t)Xh * Y * Tn;
-  tw_rows.clear();
-  tw_cy.clear();
-  tw_ct.clear();
-  add_twiddles(rg.G.px, tw_rows);
-  add_twiddles(cy.p, tw_cy);
-  add_twiddles(ct.p, tw_ct);
-  return true;
-}
 
 // ---------------------------------------------------------------------------
 // problem resolution
@@ -214,9 +37,7 @@ struct SolveSpec {
   double c_gamma = 0;      // gamma_heuristic = c_gamma * lambda / max(b)
   double g1_div = 1;       // gamma(1) = gamma_heuristic / g1_div
   double rho = 0;          // z-solve rho
-  RowGeom rg{};
-  ColGeom cy{}, ct{};
-  std::vector<cpx<double>> tw_rows, tw_cy, tw_ct;
+  LinePlan lp;             // rows over the Y Tn rows, y-lines, (video) t-lines
 };
 
 static void resolve_solve(const ccsc_solve_problem& pin, SolveSpec& S) {
@@ -275,26 +96,8 @@ static void resolve_solve(const ccsc_solve_problem& pin, SolveSpec& S) {
   }
   if (!(p.lambda_prior > 0)) throw Err(CCSC_E_INVALID, "lambda_prior must be positive (gamma heuristic)");
   // transform plans
-  if (!plan_rows(S.X, S.Y * S.Tn, S.rg))
-    throw Err(CCSC_E_UNSUPPORTED, "grid length " + std::to_string(S.X) + " has no line plan");
-  if (!plan_cols(S.Y, S.X / 2 + 1, S.cy))
-    throw Err(CCSC_E_UNSUPPORTED, "grid length " + std::to_string(S.Y) + " has no line plan");
-  const int Xh = S.X / 2 + 1;
-  S.cy.es = Xh;
-  S.cy.ninner = 1;
-  S.cy.sin = 0;
-  S.cy.sout = (int64_t)Xh * S.Y;
-  add_twiddles(S.rg.G.px, S.tw_rows);
-  add_twiddles(S.cy.p, S.tw_cy);
-  if (v3) {
-    if (!plan_cols(S.Tn, Xh, S.ct))
-      throw Err(CCSC_E_UNSUPPORTED, "grid length " + std::to_string(S.Tn) + " has no line plan");
-    S.ct.es = (int64_t)Xh * S.Y;
-    S.ct.ninner = S.Y;
-    S.ct.sin = Xh;
-    S.ct.sout = (int64_t)Xh * S.Y * S.Tn;
-    add_twiddles(S.ct.p, S.tw_ct);
-  }
+  if (const int bad = plan_lines(S.X, S.Y, S.Tn, v3, S.lp))
+    throw Err(CCSC_E_UNSUPPORTED, "grid length " + std::to_string(bad) + " has no line plan");
   if (S.F > INT32_MAX / 2 || (int64_t)S.Kc * S.W > 65535 * 4)
     throw Err(CCSC_E_UNSUPPORTED, "spectrum too large for the per-bin kernels");
   if (p.n > 65535) throw Err(CCSC_E_UNSUPPORTED, "more than 65535 images in one call");
@@ -308,6 +111,7 @@ struct Solver {
   hipStream_t st;
   int64_t n;
   DevBuf tw_r, tw_y, tw_t;
+  LinePass lines;   // twiddle tables, the unfused transforms (the iteration's passes are fused)
   DevBuf dhat, dhat_res, senergy;
   DevBuf Sz, Sx, Z, D2, D1, M, Mb, SM, XO;
   DevBuf part, sums, theta1, theta2, active;
@@ -318,44 +122,17 @@ struct Solver {
     n = S.p.n;
   }
 
-  template <typename X> static X* ptr(DevBuf& b) { return b.as<X>(); }
-  cpx<double>* tw(DevBuf& b) { return b.as<cpx<double>>(); }
-
-  void upload_tw(DevBuf& b, const std::vector<cpx<double>>& t) {
-    b.alloc(std::max<size_t>(t.size(), 1) * 16);
-    if (!t.empty()) HIPCHK(hipMemcpyAsync(b.p, t.data(), t.size() * 16, hipMemcpyHostToDevice, st));
-  }
-
-  // forward transform of `count` real grid slices (src) into spectra (dst)
-  void fwd(const double* src, cpx<double>* dst, int64_t count) {
-    RowArgs<double> a{};
-    a.S = dst;
-    a.src = src;
-    a.per_img = 1;
-    HIPCHK(launch_rows<double>(kRowFwd, a, count, S.rg, tw(tw_r), st));
-    cols(dst, -1, count);
-  }
-  void cols(cpx<double>* sp, int sign, int64_t count) {
-    if (sign < 0) {
-      HIPCHK(launch_cols<double>(sp, -1, count * S.Tn, S.cy, tw(tw_y), st));
-      if (S.nd == 3) HIPCHK(launch_cols<double>(sp, -1, count * S.Y, S.ct, tw(tw_t), st));
-    } else {
-      if (S.nd == 3) HIPCHK(launch_cols<double>(sp, +1, count * S.Y, S.ct, tw(tw_t), st));
-      HIPCHK(launch_cols<double>(sp, +1, count * S.Tn, S.cy, tw(tw_y), st));
-    }
-  }
-
   // both spectrum sets (codes, data) in one launch per line direction
   void cols2(int sign, int64_t nz, int64_t nx) {
     cpx<double>* a = Sz.as<cpx<double>>();
     cpx<double>* b = Sx.as<cpx<double>>();
-    if (sign < 0) {
-      HIPCHK(launch_cols<double>(a, -1, nz * S.Tn, S.cy, tw(tw_y), st, b, nx * S.Tn));
-      if (S.nd == 3) HIPCHK(launch_cols<double>(a, -1, nz * S.Y, S.ct, tw(tw_t), st, b, nx * S.Y));
-    } else {
-      if (S.nd == 3) HIPCHK(launch_cols<double>(a, +1, nz * S.Y, S.ct, tw(tw_t), st, b, nx * S.Y));
-      HIPCHK(launch_cols<double>(a, +1, nz * S.Tn, S.cy, tw(tw_y), st, b, nx * S.Tn));
-    }
+    auto y_lines = [&] {
+      HIPCHK(launch_cols<double>(a, sign, nz * S.Tn, S.lp.cy, lines.twy, st, b, nx * S.Tn));
+    };
+    if (sign < 0) y_lines();
+    if (S.lp.with_t)
+      HIPCHK(launch_cols<double>(a, sign, nz * S.Y, S.lp.ct, lines.twt, st, b, nx * S.Y));
+    if (sign > 0) y_lines();
   }
 
   void setup(const ccsc_solve_inputs& in) {
@@ -367,9 +144,7 @@ struct Solver {
     if (v3 && !in.psf) throw Err(CCSC_E_INVALID, "VIDEO3D needs the psf");
     const bool psnr = in.x_orig && (p.variant == CCSC_SOLVE_INPAINT2D ||
                                     p.variant == CCSC_SOLVE_POISSON2D);
-    upload_tw(tw_r, S.tw_rows);
-    upload_tw(tw_y, S.tw_cy);
-    upload_tw(tw_t, S.tw_ct);
+    lines.setup(S.lp, st, tw_r, tw_y, &tw_t);
     const int64_t P = S.P, F = S.F;
     const int Kc = S.Kc, W = S.W;
     // ---- filter spectra (psf2otf of every filter; SI:155-162, SD:100-115, SV:121-138)
@@ -393,7 +168,7 @@ struct Solver {
       HIPCHK(launch_embed_kernels<double>(kd.as<double>(), grid.as<double>(), kx, ky, kt,
                                           (int)nfilt, S.X, S.Y, S.Tn, st));
       dhat.alloc((size_t)(nfilt * F) * 16);
-      fwd(grid.as<double>(), dhat.as<cpx<double>>(), nfilt);
+      lines.r2c(grid.as<double>(), dhat.as<cpx<double>>(), nfilt);
       if (v3) {
         // dhat = psf_hat .* dhat_k (SV:131); the reconstruction keeps dhat_k (SV:109)
         dhat_res.alloc(dhat.bytes);
@@ -407,7 +182,7 @@ struct Solver {
         HIPCHK(launch_embed_kernels<double>(pd.as<double>(), pg.as<double>(), p.psf_size[0],
                                             p.psf_size[1], p.psf_size[2], 1, S.X, S.Y, S.Tn, st));
         ph.alloc((size_t)F * 16);
-        fwd(pg.as<double>(), ph.as<cpx<double>>(), 1);
+        lines.r2c(pg.as<double>(), ph.as<cpx<double>>(), 1);
         HIPCHK(launch_spec_mul<double>(dhat.as<cpx<double>>(), ph.as<cpx<double>>(), F, (int)nfilt, st));
         HIPCHK(hipStreamSynchronize(st));
       }
@@ -475,7 +250,7 @@ struct Solver {
     HIPCHK(hipMemsetAsync(Z.p, 0, Z.bytes, st));
     HIPCHK(hipMemsetAsync(D2.p, 0, D2.bytes, st));
     HIPCHK(hipMemsetAsync(D1.p, 0, D1.bytes, st));
-    part.alloc((size_t)(n * (Kc + W) * S.rg.groups * kRowParts) * 8);
+    part.alloc((size_t)(n * (Kc + W) * S.lp.rg.groups * kRowParts) * 8);
     sums.alloc((size_t)(n * kRowParts) * 8);
     active.alloc((size_t)n * 4);
     std::vector<int> ones((size_t)n, 1);
@@ -570,10 +345,10 @@ struct Solver {
     for (int i = 0; i <= max_it && live > 0; ++i) {
       const bool last = i == max_it;
       HIPCHK(launch_rows_pair<double>(last ? kRowFinalZ : kRowIterZ, code_args(i == 0), nz,
-                                      data_args(i == 0), nx, S.rg, tw(tw_r), st));
+                                      data_args(i == 0), nx, S.lp.rg, lines.twr, st));
       if (need_sums) {
         HIPCHK(launch_reduce_parts<double>(part.as<double>(), sums.as<double>(), n, S.Kc + S.W,
-                                           S.rg.groups, st));
+                                           S.lp.rg.groups, st));
         HIPCHK(hipMemcpyAsync(hs.data(), sums.p, sums.bytes, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         bool changed = false;
@@ -625,11 +400,11 @@ struct Solver {
     if (out && out->z)
       HIPCHK(hipMemcpyAsync(out->z, Z.p, Z.bytes, hipMemcpyDeviceToHost, st));
     if (out && out->res) {
-      fwd(Z.as<double>(), Sz.as<cpx<double>>(), nz);
+      lines.r2c(Z.as<double>(), Sz.as<cpx<double>>(), nz);
       const cpx<double>* dres = dhat_res.p ? dhat_res.as<cpx<double>>() : dhat.as<cpx<double>>();
       HIPCHK(launch_hs_synth<double>(dres, Sz.as<cpx<double>>(), Sx.as<cpx<double>>(), (int)S.F,
                                      S.W, S.Kc, (int)n, st));
-      cols(Sx.as<cpx<double>>(), +1, nx);
+      lines.inv_cols(Sx.as<cpx<double>>(), nx);
       RowArgs<double> a{};
       a.S = Sx.as<cpx<double>>();
       a.SM = SM.p ? SM.as<double>() : nullptr;
@@ -646,7 +421,7 @@ struct Solver {
       DevBuf res;
       res.alloc((size_t)(nx * p.sb[0] * p.sb[1] * p.sb[2]) * 8);
       a.res = res.as<double>();
-      HIPCHK(launch_rows<double>(kRowRes, a, nx, S.rg, tw(tw_r), st));
+      HIPCHK(launch_rows<double>(kRowRes, a, nx, S.lp.rg, lines.twr, st));
       HIPCHK(hipMemcpyAsync(out->res, res.p, res.bytes, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
     }

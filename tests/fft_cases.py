@@ -52,7 +52,7 @@ def line2d_grids():
     return g + [(266, 266), (70, 67)] + list(LINE2D_AUDIT)
 
 
-# the same kernels planned by gfft_plan3 (rows over Y T rows, the t lines): one grid per
+# the same kernels planned with t-lines (rows over Y T rows, the t lines): one grid per
 # signature of the x, y and t directions that (6, 5, n) with n <= 130 does not produce
 LINE3D_AUDIT = (
     (5, 6, 5), (7, 6, 5), (13, 6, 5), (18, 6, 5), (26, 6, 5), (50, 6, 5), (112, 6, 5), (144, 6, 5),

@@ -131,7 +131,7 @@ LINE2D_CHUNKS = _line2d_chunks()
 
 @pytest.mark.parametrize("chunk", list(LINE2D_CHUNKS))
 def test_line_family_2d(gpu_ctx, chunk):
-    """Global row and column line passes planned by gfft_plan (ccsc_test_gfft, T = 1)."""
+    """Global row and column line passes planned by plan_lines (ccsc_test_gfft, T = 1)."""
     from ccsc_code_iccv2017_amd.learners import gfft_test
     w = Worst(f"line family 2D, {chunk}")
     for dims in LINE2D_CHUNKS[chunk]:
@@ -145,7 +145,7 @@ LINE3D_CHUNKS = {"t_lines": [d for d in FC.line3d_grids() if d[:2] == (6, 5)],
 
 @pytest.mark.parametrize("chunk", list(LINE3D_CHUNKS))
 def test_line_family_3d(gpu_ctx, chunk):
-    """The same kernels planned by gfft_plan3: rows over the Y T rows of a slice, y lines per
+    """The same kernels planned with t-lines: rows over the Y T rows of a slice, y lines per
     plane, t lines over the Y rows."""
     from ccsc_code_iccv2017_amd.learners import gfft_test
     w = Worst(f"line family 3D, {chunk}")
