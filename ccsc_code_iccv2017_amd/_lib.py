@@ -26,6 +26,7 @@ CCSC_FP64 = 0
 CCSC_FP32 = 1  # deprecated: CCSC_E_UNSUPPORTED
 DFACTOR = {"auto": 0, "cholesky": 1, "woodbury": 2}
 TRANSPORT = {0: "none", 1: "rccl", 2: "host"}
+PAD = {"symmetric": 0, "replicate": 1, "zero": 2}   # CCSC_PAD_* (ccsc_imfilter)
 
 
 class Problem(C.Structure):
@@ -193,6 +194,10 @@ SIGNATURES = {
                                   C.c_char_p, C.c_size_t]),
     "ccsc_local_cn_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                       C.c_int32, C.c_char_p, C.c_size_t]),
+    "ccsc_imfilter": (C.c_int32, [C.c_void_p, _dp, _dp, C.c_int64, C.c_int32, _ip, _dp, _ip,
+                                  C.c_int32, C.c_char_p, C.c_size_t]),
+    "ccsc_imfilter_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                      _ip, _dp, _ip, C.c_int32, C.c_char_p, C.c_size_t]),
     "ccsc_test_fft2d": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
                                     C.c_char_p, C.c_size_t]),
     "ccsc_test_fft_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -309,6 +309,20 @@ int64_t local_cn_tiled_chunk(int64_t n, int H, int W, size_t budget);
 hipError_t launch_local_cn_tiled(const double* in, double* out, int64_t m, int H, int W,
                                  void* workspace, hipStream_t st);
 
+// ---- imfilter.hip: imfilter(A, k, 'same', 'conv', boundary) ------------------------
+// n column-major [H, W, T] fp64 arrays (device pointers, out must not overlap in) with
+// one [kh, kw, kt] kernel; boundary: CCSC_PAD_*.  `taps` (device) holds the kernel as
+// imfilter_pack_taps lays it out from the column-major host array k: [s][u][v], v fastest.
+// imfilter_ok: extents >= 1, H * W * T < 2^31, kernel extents odd and at most
+// kImfMaxExt, at most kImfMaxTaps taps.  Launches in chunks of workgroups, so any n runs.
+constexpr int kImfMaxExt = 31;
+constexpr int kImfMaxTaps = 4096;
+bool imfilter_ok(const int dims[3], const int kdims[3]);
+void imfilter_pack_taps(const double* k, const int kdims[3], double* packed);
+hipError_t launch_imfilter(const double* in, double* out, int64_t n, const int dims[3],
+                           const double* taps, const int kdims[3], int boundary,
+                           hipStream_t st);
+
 // ---- util.hip ---------------------------------------------------------------
 template <typename T>
 hipError_t launch_randn(T* out, int64_t count, uint64_t seed, uint64_t offset, hipStream_t st);

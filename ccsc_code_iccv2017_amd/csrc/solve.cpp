@@ -475,6 +475,64 @@ static void local_cn_device(ccsc_ctx* ctx, const double* in, double* out, int64_
   HIPCHK(hipStreamSynchronize(ctx->stream));   // the workspace is released on return
 }
 
+// ---- imfilter: argument checks (nothing here touches the device) --------------------
+
+struct ImfShape {
+  int dims[3], kdims[3];
+  int64_t per;      // pixels per array
+  int64_t ntaps;
+};
+
+static ImfShape imfilter_check(const ccsc_ctx* ctx, const double* in, const double* out, int64_t n,
+                               int32_t nd, const int32_t* dims, const double* k,
+                               const int32_t* kdims, int32_t boundary) {
+  if (!ctx || !in || !out || !dims || !k || !kdims)
+    throw Err(CCSC_E_INVALID, "imfilter: NULL ctx, in, out, dims, k or kdims");
+  if (n < 0) throw Err(CCSC_E_INVALID, "imfilter: n must be >= 0");
+  if (nd < 1 || nd > 3)
+    throw Err(CCSC_E_INVALID, "imfilter: nd must be 1, 2 or 3, got " + std::to_string(nd));
+  if (boundary < CCSC_PAD_SYMMETRIC || boundary > CCSC_PAD_ZERO)
+    throw Err(CCSC_E_INVALID, "imfilter: unknown boundary " + std::to_string(boundary) +
+                                  " (CCSC_PAD_SYMMETRIC, _REPLICATE or _ZERO)");
+  if (in == out)
+    throw Err(CCSC_E_INVALID, "imfilter: out must not alias in (a stencil cannot run in place)");
+  ImfShape S;
+  S.per = 1;
+  S.ntaps = 1;
+  for (int i = 0; i < 3; ++i) {
+    const std::string dim = " in dimension " + std::to_string(i + 1);
+    if (dims[i] < 1 || kdims[i] < 1)
+      throw Err(CCSC_E_INVALID, "imfilter: extents must be at least 1" + dim);
+    if (i >= nd && (dims[i] != 1 || kdims[i] != 1))
+      throw Err(CCSC_E_INVALID, "imfilter: extents past nd must be 1" + dim);
+    if (kdims[i] % 2 == 0)
+      throw Err(CCSC_E_UNSUPPORTED, "imfilter: kernel extents must be odd, got " +
+                                        std::to_string(kdims[i]) + dim);
+    if (kdims[i] > kImfMaxExt)
+      throw Err(CCSC_E_UNSUPPORTED, "imfilter: kernel extents above " +
+                                        std::to_string(kImfMaxExt) + " are not supported, got " +
+                                        std::to_string(kdims[i]) + dim);
+    S.dims[i] = dims[i];
+    S.kdims[i] = kdims[i];
+    S.ntaps *= kdims[i];
+    S.per *= dims[i];
+    if (S.per >= ((int64_t)1 << 31))
+      throw Err(CCSC_E_UNSUPPORTED, "imfilter: H * W * T must be below 2^31 pixels");
+  }
+  if (S.ntaps > kImfMaxTaps)
+    throw Err(CCSC_E_UNSUPPORTED, "imfilter: at most " + std::to_string(kImfMaxTaps) +
+                                      " taps are supported, got " + std::to_string(S.ntaps));
+  return S;
+}
+
+// The kernel's taps onto the device, in the layout the kernel reads (copied on return).
+static void imfilter_taps(const ImfShape& S, const double* k, DevBuf& taps) {
+  std::vector<double> packed((size_t)S.ntaps);
+  imfilter_pack_taps(k, S.kdims, packed.data());
+  taps.alloc(packed.size() * 8);
+  HIPCHK(hipMemcpy(taps.p, packed.data(), taps.bytes, hipMemcpyHostToDevice));
+}
+
 extern "C" {
 
 int32_t ccsc_solve_supported(const ccsc_solve_problem* p, char* err, size_t errlen) {
@@ -523,6 +581,45 @@ int32_t ccsc_local_cn(ccsc_ctx* ctx, const double* in, double* out, int64_t n, i
                             ctx->stream));
       local_cn_device(ctx, a.as<double>(), b.as<double>(), m, H, W);
       HIPCHK(hipMemcpyAsync(out + i0 * per, b.p, (size_t)(m * per) * 8, hipMemcpyDeviceToHost,
+                            ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  });
+}
+
+int32_t ccsc_imfilter_dev(ccsc_ctx* ctx, const double* in, double* out, int64_t n, int32_t nd,
+                          const int32_t dims[3], const double* k, const int32_t kdims[3],
+                          int32_t boundary, char* err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    const ImfShape S = imfilter_check(ctx, in, out, n, nd, dims, k, kdims, boundary);
+    if (n == 0) return;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf taps;
+    imfilter_taps(S, k, taps);
+    HIPCHK(launch_imfilter(in, out, n, S.dims, taps.as<double>(), S.kdims, boundary, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // the taps are released on return
+  });
+}
+
+int32_t ccsc_imfilter(ccsc_ctx* ctx, const double* in, double* out, int64_t n, int32_t nd,
+                      const int32_t dims[3], const double* k, const int32_t kdims[3],
+                      int32_t boundary, char* err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    const ImfShape S = imfilter_check(ctx, in, out, n, nd, dims, k, kdims, boundary);
+    if (n == 0) return;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf taps, a, b;
+    imfilter_taps(S, k, taps);
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (256LL << 20) / (S.per * 8)));
+    a.alloc((size_t)(chunk * S.per) * 8);
+    b.alloc(a.bytes);
+    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+      const int64_t m = std::min(chunk, n - i0);
+      HIPCHK(hipMemcpyAsync(a.p, in + i0 * S.per, (size_t)(m * S.per) * 8, hipMemcpyHostToDevice,
+                            ctx->stream));
+      HIPCHK(launch_imfilter(a.as<double>(), b.as<double>(), m, S.dims, taps.as<double>(), S.kdims,
+                             boundary, ctx->stream));
+      HIPCHK(hipMemcpyAsync(out + i0 * S.per, b.p, (size_t)(m * S.per) * 8, hipMemcpyDeviceToHost,
                             ctx->stream));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -18,6 +18,10 @@ median): images of at most 12288 pixels in one workgroup each with LDS-resident 
 convolutions, larger ones (real images, video frames) in 32 x 32 tiles over many
 workgroups per image.  The torch restatement below serves CPU tensors (tests, the CPU
 baseline).  PyTorch draws the synthetic codes and noise.
+
+imfilter / smooth_init are the drivers' imfilter(b, k, 'same', 'conv', boundary) on the GPU
+(ccsc_imfilter, csrc/imfilter.hip) for callers' own data; the synthetic cubes_23 keeps
+gauss_symmetric, its torch restatement.
 """
 from __future__ import annotations
 
@@ -238,6 +242,58 @@ def gauss_symmetric(b: np.ndarray, size: int = 13, sigma: float = 3 * 1.591,
     kk = torch.as_tensor(np.ascontiguousarray(k.T[::-1, ::-1]), dtype=t.dtype, device=device)
     o = Fnn.conv2d(t[:, None], kk[None, None])[:, 0]          # [m, Y, X]
     return np.asfortranarray(o.permute(2, 1, 0).cpu().numpy().reshape((X, Y) + rest, order="F"))
+
+
+def imfilter(a, k: np.ndarray, boundary: str = "symmetric"):
+    """MATLAB imfilter(a, k, 'same', 'conv', boundary) on the GPU (csrc/imfilter.hip): the
+    leading k.ndim (1, 2 or 3) dimensions of `a` are filtered, the others are the batch.
+    boundary: 'symmetric' (mirror, edge repeated), 'replicate' or 'zero'.  Kernel extents
+    are odd, at most 31, at most 4096 taps; anything else raises CCSCError.
+
+    `a` is a NumPy array indexed as in MATLAB ([x, y, ..., n]; goes through ccsc_imfilter
+    on the current device, returns a Fortran-ordered float64 array) or a CUDA tensor indexed
+    the same way (goes through ccsc_imfilter_dev on its device, returns a float64 CUDA
+    tensor).
+    No fallback: a missing libccsc raises."""
+    from . import _lib as L
+    from .learners import Context
+    k = np.asfortranarray(k, dtype=np.float64)
+    nd = k.ndim
+    if a.ndim < nd:
+        raise ValueError(f"a has {a.ndim} dimensions, the kernel {nd}")
+    if boundary not in L.PAD:
+        raise ValueError(f"boundary must be one of {sorted(L.PAD)}, got {boundary!r}")
+    shape = tuple(a.shape)
+    n = int(np.prod(shape[nd:], dtype=np.int64))
+    dims = (L.C.c_int32 * 3)(*(list(shape[:nd]) + [1, 1, 1])[:3])
+    kdims = (L.C.c_int32 * 3)(*(list(k.shape) + [1, 1, 1])[:3])
+    eb = L.errbuf()
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda:
+            raise ValueError("imfilter takes a NumPy array or a CUDA tensor")
+        rev = tuple(range(a.ndim - 1, -1, -1))
+        x = a.to(torch.float64).permute(rev).contiguous()     # memory: column-major a
+        out = torch.empty_like(x)
+        dev = a.device.index if a.device.index is not None else torch.cuda.current_device()
+        torch.cuda.synchronize(a.device)
+        with Context(dev) as ctx:   # one stream for this call (no context outlives it)
+            L.check(L.lib().ccsc_imfilter_dev(ctx.ptr, x.data_ptr(), out.data_ptr(), n, nd, dims,
+                                              L.dptr(k), kdims, L.PAD[boundary], eb, len(eb)), eb)
+        return out.permute(rev)
+    x = np.asfortranarray(a, dtype=np.float64)
+    out = np.empty(shape, order="F")
+    with Context(torch.cuda.current_device()) as ctx:
+        L.check(L.lib().ccsc_imfilter(ctx.ptr, L.dptr(x), L.dptr(out), n, nd, dims, L.dptr(k),
+                                      kdims, L.PAD[boundary], eb, len(eb)), eb)
+    return out
+
+
+def smooth_init(b, size: int = 13, sigma: float = 3 * 1.591):
+    """The drivers' smooth_init (learn_hyperspectral.m:16-17 and the three reconstruction
+    drivers; size 15 in reconstruct_subsampling_video.m:50-51):
+    imfilter(b, fspecial('gaussian', [size size], sigma), 'same', 'conv', 'symmetric') over
+    the first two dims of b, on the GPU (imfilter above)."""
+    return imfilter(b, fspecial_gaussian(size, sigma), "symmetric")
 
 
 def cubes_23(n: int, size=(100, 100), W: int = 31, K: int = 100, psf: int = 11,

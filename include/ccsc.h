@@ -350,6 +350,45 @@ int32_t ccsc_local_cn(ccsc_ctx* ctx, const double* in, double* out, int64_t n, i
 int32_t ccsc_local_cn_dev(ccsc_ctx* ctx, const double* in, double* out, int64_t n, int32_t H,
                           int32_t W, char* err, size_t errlen);
 
+/* N-dimensional image filtering: imfilter(A, k, 'same', 'conv', <boundary>), the call
+ * with which the reference's drivers compute smooth_init (the low-pass image that
+ * ccsc_learn_hs23 and ccsc_solve_inputs.smooth_init take) and blur their data:
+ *   k = fspecial('gaussian', [13 13], 3*1.591); imfilter(b, k, 'same', 'conv', 'symmetric')
+ *     2-3D/DictionaryLearning/learn_hyperspectral.m:16-17
+ *     2-3D/Demosaicing/reconstruct_subsampling_hyperspectral.m:54-55
+ *     4D/ViewSynthesis/reconstruct_subsampling_lightfield.m:58-59
+ *     3D/Deblurring/reconstruct_subsampling_video.m:50-51 (15x15), :40 (its 3x3x3 psf)
+ *   image_helpers/CreateImages.m:388-399 'box_cn' (imfilter 'replicate'),
+ *   :371-387 'laplacian_cn' (conv2 'same': zero padding).
+ * in/out: n column-major float64 arrays of nd = 1, 2 or 3 dimensions dims = [H, W, T];
+ * k: one column-major float64 kernel of the same nd, kdims = [kh, kw, kt]; unused trailing
+ * entries of dims and kdims are 1 (a 2D kernel over the planes of a 3D array is kt = 1).
+ * With the zero-based centre c = (extent - 1) / 2,
+ *   out[i, j, t] = sum_{u,v,s} k[u, v, s] * A_pad[i + c1 - u, j + c2 - v, t + c3 - s]
+ * (convolution, not correlation), accumulated s outer, v middle, u inner, ascending, one
+ * fma per tap from 0: bitwise reproducible and independent of the batch.  boundary says
+ * what A_pad reads outside A. */
+#define CCSC_PAD_SYMMETRIC 0 /* mirror, edge sample repeated: m = i mod 2N, m < N ? m : 2N-1-m
+                                (any half-width, any extent >= 1)                         */
+#define CCSC_PAD_REPLICATE 1 /* clamp the index                                          */
+#define CCSC_PAD_ZERO 2      /* out-of-range samples are 0                               */
+/* Limits: kernel extents odd, 1..31 each, at most 4096 taps; image extents >= 1 with
+ * H * W * T < 2^31: an even or larger extent, more taps or more pixels are
+ * CCSC_E_UNSUPPORTED with the reason.  NULL pointers, n < 0, nd outside 1..3, an extent
+ * < 1, a trailing extent that is not 1, an unknown boundary and out == in (a stencil
+ * cannot run in place) are CCSC_E_INVALID.  Both entry points validate before they touch
+ * the device; n == 0 is CCSC_OK and launches nothing.
+ * ccsc_imfilter takes host arrays and stages them in chunks of images of at most 256 MiB
+ * per buffer (a single larger image still gets its own); ccsc_imfilter_dev takes in/out
+ * on the context's device (e.g. torch tensors), ordered on the context's stream,
+ * synchronised on return.  k is a host array for both. */
+int32_t ccsc_imfilter(ccsc_ctx* ctx, const double* in, double* out, int64_t n, int32_t nd,
+                      const int32_t dims[3], const double* k, const int32_t kdims[3],
+                      int32_t boundary, char* err, size_t errlen);
+int32_t ccsc_imfilter_dev(ccsc_ctx* ctx, const double* in, double* out, int64_t n, int32_t nd,
+                          const int32_t dims[3], const double* k, const int32_t kdims[3],
+                          int32_t boundary, char* err, size_t errlen);
+
 /* ---- kernel-level entry points (parity tests of single stages) ---------- */
 /* 2D R2C of `count` real slices [X,Y] -> half spectra [Y][X/2+1] (re,im). */
 int32_t ccsc_test_fft2d(ccsc_ctx* ctx, int32_t X, int32_t Y, int32_t count, const double* in,
