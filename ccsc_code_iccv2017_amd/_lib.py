@@ -198,6 +198,20 @@ SIGNATURES = {
                                   C.c_int32, C.c_char_p, C.c_size_t]),
     "ccsc_imfilter_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                       _ip, _dp, _ip, C.c_int32, C.c_char_p, C.c_size_t]),
+    "ccsc_nn_fill": (C.c_int32, [C.c_void_p, _dp, _dp, _dp, _ip, C.c_int64, C.c_int32, C.c_int32,
+                                 C.c_char_p, C.c_size_t]),
+    "ccsc_nn_fill_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int64, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
+    "ccsc_standardize": (C.c_int32, [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int64, C.c_int64,
+                                     C.c_char_p, C.c_size_t]),
+    "ccsc_standardize_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.c_int64, C.c_char_p,
+                                         C.c_size_t]),
+    "ccsc_unstandardize": (C.c_int32, [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int64, C.c_int64,
+                                       C.c_char_p, C.c_size_t]),
+    "ccsc_unstandardize_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int64, C.c_int64, C.c_char_p,
+                                           C.c_size_t]),
     "ccsc_test_fft2d": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
                                     C.c_char_p, C.c_size_t]),
     "ccsc_test_fft_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -323,6 +323,25 @@ hipError_t launch_imfilter(const double* in, double* out, int64_t n, const int d
                            const double* taps, const int kdims[3], int boundary,
                            hipStream_t st);
 
+// ---- prep.hip: nearest-sample fill and per-plane standardisation ---------------------
+// Fill: n column-major [H, W] fp64 planes (device pointers).  known: NULL (a sample is
+// in != 0) or planes of the same shape (a sample is known != 0); out may be in, never
+// known; idx: NULL or n * H * W int32; r: n * H * W int32 of workspace.
+// nn_fill_ok: 1 <= H, W <= kFillMaxExt (a squared distance fits int32), H * W < 2^31.
+constexpr int kFillMaxExt = 32768;
+bool nn_fill_ok(int H, int W);
+hipError_t launch_nn_fill(const double* in, const double* known, double* out, int* idx, int* r,
+                          int64_t n, int H, int W, hipStream_t st);
+// Standardise: `planes` runs of N contiguous values (device pointers), mean and sdev one
+// value per plane, out may be in; workspace: standardize_ws_bytes(planes, N).
+// standardize_ok: 2 <= N < 2^31.
+bool standardize_ok(int64_t N);
+int64_t standardize_ws_bytes(int64_t planes, int64_t N);
+hipError_t launch_standardize(const double* in, double* out, double* mean, double* sdev,
+                              int64_t planes, int64_t N, void* workspace, hipStream_t st);
+hipError_t launch_unstandardize(const double* in, double* out, const double* mean,
+                                const double* sdev, int64_t planes, int64_t N, hipStream_t st);
+
 // ---- util.hip ---------------------------------------------------------------
 template <typename T>
 hipError_t launch_randn(T* out, int64_t count, uint64_t seed, uint64_t offset, hipStream_t st);

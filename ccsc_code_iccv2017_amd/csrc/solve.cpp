@@ -533,6 +533,41 @@ static void imfilter_taps(const ImfShape& S, const double* k, DevBuf& taps) {
   HIPCHK(hipMemcpy(taps.p, packed.data(), taps.bytes, hipMemcpyHostToDevice));
 }
 
+// ---- nn_fill, standardize: argument checks (nothing here touches the device) ----------
+
+static void nn_fill_check(const ccsc_ctx* ctx, const double* in, const double* known,
+                          const double* out, int64_t n, int32_t H, int32_t W) {
+  if (!ctx || !in || !out) throw Err(CCSC_E_INVALID, "nn_fill: NULL ctx, in or out");
+  if (n < 0) throw Err(CCSC_E_INVALID, "nn_fill: n must be >= 0");
+  if (H < 1 || W < 1) throw Err(CCSC_E_INVALID, "nn_fill: extents must be at least 1");
+  if (known && known == out)
+    throw Err(CCSC_E_INVALID, "nn_fill: out must not alias known (the fill would overwrite "
+                              "the mask it reads)");
+  if (H > kFillMaxExt || W > kFillMaxExt)
+    throw Err(CCSC_E_UNSUPPORTED, "nn_fill: extents above " + std::to_string(kFillMaxExt) +
+                                      " are not supported (a squared distance must fit int32; "
+                                      "H * W then stays below 2^31)");
+}
+
+// Planes per launch group: the int32 workspace (and a host entry's staging buffers) stay
+// within 256 MiB each; a single larger plane still gets its own.
+static int64_t prep_chunk(int64_t n, int64_t per) {
+  return std::max<int64_t>(1, std::min<int64_t>(n, (256LL << 20) / (per * 8)));
+}
+
+static void standardize_check(const char* what, const ccsc_ctx* ctx, const double* in,
+                              const double* out, const double* mean, const double* sdev,
+                              int64_t planes, int64_t N) {
+  const std::string w(what);
+  if (!ctx || !in || !out || !mean || !sdev)
+    throw Err(CCSC_E_INVALID, w + ": NULL ctx, in, out, mean or sdev");
+  if (planes < 0) throw Err(CCSC_E_INVALID, w + ": planes must be >= 0");
+  if (N < 2)
+    throw Err(CCSC_E_INVALID, w + ": N must be at least 2 (std(., 0, 2) divides by N - 1)");
+  if (!standardize_ok(N))
+    throw Err(CCSC_E_UNSUPPORTED, w + ": N must be below 2^31 values per plane");
+}
+
 extern "C" {
 
 int32_t ccsc_solve_supported(const ccsc_solve_problem* p, char* err, size_t errlen) {
@@ -620,6 +655,133 @@ int32_t ccsc_imfilter(ccsc_ctx* ctx, const double* in, double* out, int64_t n, i
       HIPCHK(launch_imfilter(a.as<double>(), b.as<double>(), m, S.dims, taps.as<double>(), S.kdims,
                              boundary, ctx->stream));
       HIPCHK(hipMemcpyAsync(out + i0 * S.per, b.p, (size_t)(m * S.per) * 8, hipMemcpyDeviceToHost,
+                            ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  });
+}
+
+int32_t ccsc_nn_fill_dev(ccsc_ctx* ctx, const double* in, const double* known, double* out,
+                         int32_t* idx, int64_t n, int32_t H, int32_t W, char* err,
+                         size_t errlen) {
+  return guarded(err, errlen, [&] {
+    nn_fill_check(ctx, in, known, out, n, H, W);
+    if (n == 0) return;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t per = (int64_t)H * W;
+    const int64_t chunk = prep_chunk(n, per);
+    DevBuf r;
+    r.alloc((size_t)(chunk * per) * 4);
+    for (int64_t i0 = 0; i0 < n; i0 += chunk)
+      HIPCHK(launch_nn_fill(in + i0 * per, known ? known + i0 * per : nullptr, out + i0 * per,
+                            idx ? idx + i0 * per : nullptr, r.as<int>(), std::min(chunk, n - i0),
+                            H, W, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // the workspace is released on return
+  });
+}
+
+int32_t ccsc_nn_fill(ccsc_ctx* ctx, const double* in, const double* known, double* out,
+                     int32_t* idx, int64_t n, int32_t H, int32_t W, char* err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    nn_fill_check(ctx, in, known, out, n, H, W);
+    if (n == 0) return;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t per = (int64_t)H * W;
+    const int64_t chunk = prep_chunk(n, per);
+    DevBuf a, k, ix, r;
+    a.alloc((size_t)(chunk * per) * 8);          // filled in place
+    if (known) k.alloc(a.bytes);
+    if (idx) ix.alloc((size_t)(chunk * per) * 4);
+    r.alloc((size_t)(chunk * per) * 4);
+    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+      const int64_t m = std::min(chunk, n - i0);
+      const size_t cnt = (size_t)(m * per);
+      HIPCHK(hipMemcpyAsync(a.p, in + i0 * per, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+      if (known)
+        HIPCHK(hipMemcpyAsync(k.p, known + i0 * per, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(launch_nn_fill(a.as<double>(), k.as<double>(), a.as<double>(), ix.as<int>(),
+                            r.as<int>(), m, H, W, ctx->stream));
+      HIPCHK(hipMemcpyAsync(out + i0 * per, a.p, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+      if (idx)
+        HIPCHK(hipMemcpyAsync(idx + i0 * per, ix.p, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  });
+}
+
+int32_t ccsc_standardize_dev(ccsc_ctx* ctx, const double* in, double* out, double* mean,
+                             double* sdev, int64_t planes, int64_t N, char* err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    standardize_check("standardize", ctx, in, out, mean, sdev, planes, N);
+    if (planes == 0) return;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevBuf ws;
+    ws.alloc((size_t)standardize_ws_bytes(planes, N));
+    HIPCHK(launch_standardize(in, out, mean, sdev, planes, N, ws.p, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // the workspace is released on return
+  });
+}
+
+int32_t ccsc_standardize(ccsc_ctx* ctx, const double* in, double* out, double* mean, double* sdev,
+                         int64_t planes, int64_t N, char* err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    standardize_check("standardize", ctx, in, out, mean, sdev, planes, N);
+    if (planes == 0) return;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t chunk = prep_chunk(planes, N);
+    DevBuf a, ms, ws;
+    a.alloc((size_t)(chunk * N) * 8);            // normalised in place
+    ms.alloc((size_t)chunk * 16);                // the chunk's means, then its sdevs
+    ws.alloc((size_t)standardize_ws_bytes(chunk, N));
+    for (int64_t i0 = 0; i0 < planes; i0 += chunk) {
+      const int64_t m = std::min(chunk, planes - i0);
+      double* dm = ms.as<double>();
+      double* ds = dm + chunk;
+      HIPCHK(hipMemcpyAsync(a.p, in + i0 * N, (size_t)(m * N) * 8, hipMemcpyHostToDevice,
+                            ctx->stream));
+      HIPCHK(launch_standardize(a.as<double>(), a.as<double>(), dm, ds, m, N, ws.p, ctx->stream));
+      HIPCHK(hipMemcpyAsync(out + i0 * N, a.p, (size_t)(m * N) * 8, hipMemcpyDeviceToHost,
+                            ctx->stream));
+      HIPCHK(hipMemcpyAsync(mean + i0, dm, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipMemcpyAsync(sdev + i0, ds, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  });
+}
+
+int32_t ccsc_unstandardize_dev(ccsc_ctx* ctx, const double* in, double* out, const double* mean,
+                               const double* sdev, int64_t planes, int64_t N, char* err,
+                               size_t errlen) {
+  return guarded(err, errlen, [&] {
+    standardize_check("unstandardize", ctx, in, out, mean, sdev, planes, N);
+    if (planes == 0) return;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_unstandardize(in, out, mean, sdev, planes, N, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  });
+}
+
+int32_t ccsc_unstandardize(ccsc_ctx* ctx, const double* in, double* out, const double* mean,
+                           const double* sdev, int64_t planes, int64_t N, char* err,
+                           size_t errlen) {
+  return guarded(err, errlen, [&] {
+    standardize_check("unstandardize", ctx, in, out, mean, sdev, planes, N);
+    if (planes == 0) return;
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t chunk = prep_chunk(planes, N);
+    DevBuf a, ms;
+    a.alloc((size_t)(chunk * N) * 8);            // restored in place
+    ms.alloc((size_t)chunk * 16);
+    for (int64_t i0 = 0; i0 < planes; i0 += chunk) {
+      const int64_t m = std::min(chunk, planes - i0);
+      double* dm = ms.as<double>();
+      double* ds = dm + chunk;
+      HIPCHK(hipMemcpyAsync(a.p, in + i0 * N, (size_t)(m * N) * 8, hipMemcpyHostToDevice,
+                            ctx->stream));
+      HIPCHK(hipMemcpyAsync(dm, mean + i0, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(hipMemcpyAsync(ds, sdev + i0, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
+      HIPCHK(launch_unstandardize(a.as<double>(), a.as<double>(), dm, ds, m, N, ctx->stream));
+      HIPCHK(hipMemcpyAsync(out + i0 * N, a.p, (size_t)(m * N) * 8, hipMemcpyDeviceToHost,
                             ctx->stream));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));

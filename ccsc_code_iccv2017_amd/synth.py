@@ -22,6 +22,11 @@ baseline).  PyTorch draws the synthetic codes and noise.
 imfilter / smooth_init are the drivers' imfilter(b, k, 'same', 'conv', boundary) on the GPU
 (ccsc_imfilter, csrc/imfilter.hip) for callers' own data; the synthetic cubes_23 keeps
 gauss_symmetric, its torch restatement.
+
+nn_fill, standardize / unstandardize and interp_views are the remaining preparation steps of
+the four reconstruction drivers (the demosaicing driver's nearest-sample fill, the video,
+light-field and Poisson drivers' per-plane normalisation, the light-field driver's view
+interpolation); the first two run in csrc/prep.hip behind ccsc_nn_fill and ccsc_standardize.
 """
 from __future__ import annotations
 
@@ -294,6 +299,164 @@ def smooth_init(b, size: int = 13, sigma: float = 3 * 1.591):
     imfilter(b, fspecial('gaussian', [size size], sigma), 'same', 'conv', 'symmetric') over
     the first two dims of b, on the GPU (imfilter above)."""
     return imfilter(b, fspecial_gaussian(size, sigma), "symmetric")
+
+
+def _reversed(a: torch.Tensor, dtype):
+    """(column-major memory of the CUDA tensor `a` as a contiguous tensor, the permutation)."""
+    rev = tuple(range(a.ndim - 1, -1, -1))
+    return a.to(dtype).permute(rev).contiguous(), rev
+
+
+def nn_fill(a, known=None, return_index: bool = False):
+    """The demosaicing driver's nearest-neighbour fill
+    (reconstruct_subsampling_hyperspectral.m:43-51) on the GPU (csrc/prep.hip), per plane:
+    [~, idx] = bwdist(a ~= 0); a(a == 0) = a(idx(a == 0)).  The leading two dims of `a` are
+    the plane, the others the batch.  A pixel is a sample where known != 0 (known has a's
+    shape), or where a != 0 if known is None; every other pixel takes the value of the
+    nearest sample by exact Euclidean distance, the smallest column-major index among
+    equally near ones; a plane without a sample is returned unchanged.  With return_index
+    the zero-based column-major index of the source pixel within its plane comes back too
+    (int32, a's shape; -1 in a plane without a sample).
+
+    `a` is a NumPy array (ccsc_nn_fill on the current device; Fortran-ordered float64 back)
+    or a CUDA tensor (ccsc_nn_fill_dev on its device; CUDA tensors back), as for imfilter.
+    No fallback: a missing libccsc raises."""
+    from . import _lib as L
+    from .learners import Context
+    if a.ndim < 2:
+        raise ValueError(f"a has {a.ndim} dimensions, a plane has 2")
+    shape = tuple(a.shape)
+    if known is not None and tuple(known.shape) != shape:
+        raise ValueError("known must have the shape of a")
+    H, W = shape[:2]
+    n = int(np.prod(shape[2:], dtype=np.int64))
+    eb = L.errbuf()
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda or (known is not None and not (isinstance(known, torch.Tensor)
+                                                        and known.device == a.device)):
+            raise ValueError("nn_fill takes NumPy arrays or CUDA tensors on one device")
+        x, rev = _reversed(a, torch.float64)
+        out = torch.empty_like(x)
+        k = None if known is None else _reversed(known, torch.float64)[0]
+        idx = torch.empty(x.shape, dtype=torch.int32, device=x.device) if return_index else None
+        dev = a.device.index if a.device.index is not None else torch.cuda.current_device()
+        torch.cuda.synchronize(a.device)
+        with Context(dev) as ctx:   # one stream for this call (no context outlives it)
+            L.check(L.lib().ccsc_nn_fill_dev(ctx.ptr, x.data_ptr(),
+                                             None if k is None else k.data_ptr(), out.data_ptr(),
+                                             None if idx is None else idx.data_ptr(), n, H, W,
+                                             eb, len(eb)), eb)
+        return (out.permute(rev), idx.permute(rev)) if return_index else out.permute(rev)
+    x = np.asfortranarray(a, dtype=np.float64)
+    k = None if known is None else np.asfortranarray(known, dtype=np.float64)
+    out = np.empty(shape, order="F")
+    idx = np.empty(shape, dtype=np.int32, order="F") if return_index else None
+    with Context(torch.cuda.current_device()) as ctx:
+        L.check(L.lib().ccsc_nn_fill(ctx.ptr, L.dptr(x), L.dptr(k), L.dptr(out), L.iptr(idx), n,
+                                     H, W, eb, len(eb)), eb)
+    return (out, idx) if return_index else out
+
+
+def _planes(shape, plane_dims: int):
+    if not 1 <= plane_dims <= len(shape):
+        raise ValueError(f"plane_dims must be in 1..{len(shape)}, got {plane_dims}")
+    N = int(np.prod(shape[:plane_dims], dtype=np.int64))
+    return N, int(np.prod(shape[plane_dims:], dtype=np.int64)), tuple(shape[plane_dims:])
+
+
+def standardize(b, plane_dims: int):
+    """The drivers' per-plane normalisation (reconstruct_subsampling_video.m:42-47 per frame,
+    reconstruct_subsampling_lightfield.m:36-41 per view, reconstruct_poisson_noise.m:49-54 per
+    image) on the GPU (csrc/prep.hip): the leading plane_dims dims of b form one plane (2 for
+    frames and views, b.ndim for a whole image), the others the batch.  Returns
+    (nb, mean, sdev) with nb = (b - mean) / sdev per plane, mean = mean(v, 2) and
+    sdev = std(v, 0, 2) (two-pass, N - 1) of the batch's shape.  A NumPy array goes through
+    ccsc_standardize (Fortran-ordered float64 back), a CUDA tensor through
+    ccsc_standardize_dev (CUDA tensors back).  Bitwise reproducible and independent of the
+    batch.  No fallback: a missing libccsc raises."""
+    from . import _lib as L
+    from .learners import Context
+    shape = tuple(b.shape)
+    N, planes, rest = _planes(shape, plane_dims)
+    eb = L.errbuf()
+    if isinstance(b, torch.Tensor):
+        if not b.is_cuda:
+            raise ValueError("standardize takes a NumPy array or a CUDA tensor")
+        x, rev = _reversed(b, torch.float64)
+        out = torch.empty_like(x)
+        mean = torch.empty(rest[::-1], dtype=torch.float64, device=x.device)
+        sdev = torch.empty_like(mean)
+        rrev = tuple(range(len(rest) - 1, -1, -1))
+        dev = b.device.index if b.device.index is not None else torch.cuda.current_device()
+        torch.cuda.synchronize(b.device)
+        with Context(dev) as ctx:
+            L.check(L.lib().ccsc_standardize_dev(ctx.ptr, x.data_ptr(), out.data_ptr(),
+                                                 mean.data_ptr(), sdev.data_ptr(), planes, N, eb,
+                                                 len(eb)), eb)
+        return out.permute(rev), mean.permute(rrev), sdev.permute(rrev)
+    x = np.asfortranarray(b, dtype=np.float64)
+    out = np.empty(shape, order="F")
+    mean = np.empty(rest, order="F")
+    sdev = np.empty(rest, order="F")
+    with Context(torch.cuda.current_device()) as ctx:
+        L.check(L.lib().ccsc_standardize(ctx.ptr, L.dptr(x), L.dptr(out), L.dptr(mean),
+                                         L.dptr(sdev), planes, N, eb, len(eb)), eb)
+    return out, mean, sdev
+
+
+def unstandardize(x, mean, sdev, plane_dims: int):
+    """The drivers' un-normalisation after the solve, sig_rec .* vssd + vemm
+    (reconstruct_subsampling_video.m:63-68 and its siblings): x * sdev + mean per plane, a
+    multiply and then an add, bit for bit NumPy's x * s + m.  mean and sdev are what
+    standardize returned (the shape of x's batch dims; NumPy arrays with a NumPy x, CUDA
+    tensors with a CUDA x)."""
+    from . import _lib as L
+    from .learners import Context
+    shape = tuple(x.shape)
+    N, planes, rest = _planes(shape, plane_dims)
+    if tuple(mean.shape) != rest or tuple(sdev.shape) != rest:
+        raise ValueError(f"mean and sdev must have the shape {rest} of x's batch dims")
+    eb = L.errbuf()
+    if isinstance(x, torch.Tensor):
+        if not (x.is_cuda and isinstance(mean, torch.Tensor) and isinstance(sdev, torch.Tensor)
+                and mean.device == x.device and sdev.device == x.device):
+            raise ValueError("unstandardize takes NumPy arrays or CUDA tensors on one device")
+        v, rev = _reversed(x, torch.float64)
+        m = _reversed(mean, torch.float64)[0]
+        s = _reversed(sdev, torch.float64)[0]
+        out = torch.empty_like(v)
+        dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+        torch.cuda.synchronize(x.device)
+        with Context(dev) as ctx:
+            L.check(L.lib().ccsc_unstandardize_dev(ctx.ptr, v.data_ptr(), out.data_ptr(),
+                                                   m.data_ptr(), s.data_ptr(), planes, N, eb,
+                                                   len(eb)), eb)
+        return out.permute(rev)
+    v = np.asfortranarray(x, dtype=np.float64)
+    m = np.asfortranarray(mean, dtype=np.float64)
+    s = np.asfortranarray(sdev, dtype=np.float64)
+    out = np.empty(shape, order="F")
+    with Context(torch.cuda.current_device()) as ctx:
+        L.check(L.lib().ccsc_unstandardize(ctx.ptr, L.dptr(v), L.dptr(out), L.dptr(m), L.dptr(s),
+                                           planes, N, eb, len(eb)), eb)
+    return out
+
+
+def interp_views(signal_sparse):
+    """The light-field driver's "quickly interpolate blocked out views"
+    (reconstruct_subsampling_lightfield.m:47-51) on an [x, y, U, U] NumPy array or tensor:
+    for ss = 2 .. U - 1 in order, the inner views of row ss and then of column ss become the
+    mean of their two neighbours across it, so ss = 3 reads what ss = 2 wrote.  Returns a new
+    array; the caller puts the kept centre view back, as the driver does at :52."""
+    if signal_sparse.ndim != 4 or signal_sparse.shape[2] != signal_sparse.shape[3] \
+            or signal_sparse.shape[2] < 3:
+        raise ValueError("interp_views takes an [x, y, U, U] array with U >= 3")
+    s = signal_sparse.clone() if isinstance(signal_sparse, torch.Tensor) else \
+        np.array(signal_sparse, dtype=np.float64, order="F")
+    for ss in range(1, s.shape[2] - 1):           # MATLAB's ss = ss + 1
+        s[:, :, ss, 1:-1] = (s[:, :, ss + 1, 1:-1] + s[:, :, ss - 1, 1:-1]) / 2
+        s[:, :, 1:-1, ss] = (s[:, :, 1:-1, ss + 1] + s[:, :, 1:-1, ss - 1]) / 2
+    return s
 
 
 def cubes_23(n: int, size=(100, 100), W: int = 31, K: int = 100, psf: int = 11,

@@ -389,6 +389,66 @@ int32_t ccsc_imfilter_dev(ccsc_ctx* ctx, const double* in, double* out, int64_t 
                           const int32_t dims[3], const double* k, const int32_t kdims[3],
                           int32_t boundary, char* err, size_t errlen);
 
+/* Nearest-sample fill of the unsampled pixels, per wavelength plane
+ *   [~, idx] = bwdist(a ~= 0); a(a == 0) = a(idx(a == 0));
+ *     2-3D/Demosaicing/reconstruct_subsampling_hyperspectral.m:43-51
+ * (the filled cube is what that driver filters smooth_init from, :54-55).
+ * in/out: n column-major [H, W] float64 planes; known: NULL or the same shape; idx: NULL or
+ * n * H * W int32.  Per plane, independent of the other planes: pixel q is a sample iff
+ * known[q] != 0, or in[q] != 0 where known is NULL (the reference's a ~= 0: a NaN is a
+ * sample, -0.0 is not).  A sample keeps out[q] = in[q], idx[q] = q, the zero-based
+ * column-major index i + H * j.  Any other pixel gets out[q] = in[s], idx[q] = s, with s the
+ * sample that minimises the exact squared Euclidean distance (i - i')^2 + (j - j')^2,
+ * compared in integer arithmetic; among equally near samples the smallest column-major
+ * index wins (the smallest j', then the smallest i').  bwdist does not document which of
+ * several nearest samples it reports, so ties cannot be pinned to MATLAB: parity here means
+ * exact distances.  A plane without a sample has out = in and idx = -1 everywhere (the
+ * reference would index with 0 and stop).  out may be in: only non-samples are written and
+ * only samples are read.  Results are bitwise reproducible, independent of the batch and
+ * equal between the two entry points.
+ * Limits: 1 <= H, W <= 32768, so that a squared distance fits int32 and H * W < 2^31; a
+ * larger extent is CCSC_E_UNSUPPORTED with the reason.  NULL in or out, n < 0, an extent < 1 and
+ * known == out are CCSC_E_INVALID.  Both entry points validate before they touch the
+ * device; n == 0 is CCSC_OK and launches nothing.  ccsc_nn_fill takes host arrays and stages
+ * them in chunks of planes of at most 256 MiB per buffer; ccsc_nn_fill_dev takes arrays on
+ * the context's device, is ordered on the context's stream and synchronised on return.  The
+ * int32 workspace of one entry per pixel of a chunk is allocated inside the call and freed
+ * before it returns. */
+int32_t ccsc_nn_fill(ccsc_ctx* ctx, const double* in, const double* known, double* out,
+                     int32_t* idx, int64_t n, int32_t H, int32_t W, char* err, size_t errlen);
+int32_t ccsc_nn_fill_dev(ccsc_ctx* ctx, const double* in, const double* known, double* out,
+                         int32_t* idx, int64_t n, int32_t H, int32_t W, char* err,
+                         size_t errlen);
+
+/* Per-plane standardisation and its inverse after the solve ("all data should be similarly
+ * normalized"):
+ *   veam = mean(v, 2); vstd = std(v, 0, 2); nb = (v - veam) ./ vstd; ... sig_rec .* vssd + vemm
+ *     3D/Deblurring/reconstruct_subsampling_video.m:42-47, 63-68          per frame
+ *     4D/ViewSynthesis/reconstruct_subsampling_lightfield.m:36-41, 67-72  per view
+ *     2D/Poisson_deconv/reconstruct_poisson_noise.m:49-54, 98-102         per image (commented)
+ * in/out: `planes` runs of N contiguous float64 values (a frame, a view or an image in
+ * MATLAB order); mean, sdev: one value per plane; out may be in.  As MATLAB's two-pass std:
+ *   mean_p = (sum x) / N,  sdev_p = sqrt(sum (x - mean_p)^2 / (N - 1)) with the rounded mean_p,
+ *   standardize:    out = (x - mean_p) / sdev_p   (a true division)
+ *   unstandardize:  out = in * sdev_p + mean_p    (a multiply, then an add: two roundings)
+ * A plane of zero spread divides by zero as the reference does.  Both sums are taken with
+ * one fixed tree whose shape depends on N alone (no atomics), so results are bitwise
+ * reproducible, independent of `planes` and equal between the entry points.
+ * Limits: 2 <= N < 2^31; N < 2, planes < 0 and NULL pointers are CCSC_E_INVALID, a larger N
+ * is CCSC_E_UNSUPPORTED; planes == 0 is CCSC_OK and launches nothing.  The host entries
+ * stage planes in chunks of at most 256 MiB; the _dev entries take every array on the
+ * context's device, are ordered on the context's stream and synchronised on return. */
+int32_t ccsc_standardize(ccsc_ctx* ctx, const double* in, double* out, double* mean, double* sdev,
+                         int64_t planes, int64_t N, char* err, size_t errlen);
+int32_t ccsc_standardize_dev(ccsc_ctx* ctx, const double* in, double* out, double* mean,
+                             double* sdev, int64_t planes, int64_t N, char* err, size_t errlen);
+int32_t ccsc_unstandardize(ccsc_ctx* ctx, const double* in, double* out, const double* mean,
+                           const double* sdev, int64_t planes, int64_t N, char* err,
+                           size_t errlen);
+int32_t ccsc_unstandardize_dev(ccsc_ctx* ctx, const double* in, double* out, const double* mean,
+                               const double* sdev, int64_t planes, int64_t N, char* err,
+                               size_t errlen);
+
 /* ---- kernel-level entry points (parity tests of single stages) ---------- */
 /* 2D R2C of `count` real slices [X,Y] -> half spectra [Y][X/2+1] (re,im). */
 int32_t ccsc_test_fft2d(ccsc_ctx* ctx, int32_t X, int32_t Y, int32_t count, const double* in,
