@@ -265,6 +265,11 @@ struct Session2D {
   // current iterate's z (its test is done), ZT_NONE: nothing (y, or stale).
   enum { ZT_NONE, ZT_PREV, ZT_CUR };
   int zt = ZT_NONE;
+  // rt.zemit (tol = 0): `yz` holds the code spectra of the current state, [np][K][F] in
+  // bin-slot order as the phase's last z-launch emitted them (twice fft2(u - y), without
+  // the term of w).  Set by that launch alone; cleared by every other z-launch and by
+  // whatever writes `yz` (materialize_z).  The D-precompute reads them when it is set.
+  bool cz_valid = false;
   // 3D: t-FFT twiddles, objective scratch (also the global path's)
   DevBuf &twt = buf[b2::twt], &oacc = buf[b2::oacc], &odz = buf[b2::odz];
   // 2D slices past one CU's LDS (Geom::gp): global line passes (recon.hip), and the real
@@ -351,12 +356,7 @@ struct Session2D {
 
   // the objective is refreshed after every d- / z-iteration (the reference's verbose rules
   // are the same for both phases)
-  bool verbose_refresh() const {
-    if (p.variant == CCSC_DPAR) return p.verbose == CCSC_VERBOSE_BRIEF;  // dP:126,161
-    if (p.variant == CCSC_L4D) return p.verbose == CCSC_VERBOSE_ALL;     // L4:135,170
-    if (p.variant == CCSC_L3D) return p.verbose == CCSC_VERBOSE_ALL;     // L3:145,185
-    return p.verbose != CCSC_VERBOSE_NONE;                               // dZ:127,165
-  }
+  bool verbose_refresh() const { return objective_refresh(p); }   // (plan.cpp: the route reads it too)
 
   Session2D(ccsc_ctx* c, const ccsc_problem& pin, const double* b, const double* d0,
             const double* z0)
@@ -573,7 +573,10 @@ struct Session2D {
   // their state a = z + y (kernels3d.hip, zstep.hip)
   // more: another z-iteration follows directly (3D: its forward plane transform is fused
   // into this one's inverse, c_ready)
-  ZTests zstep_iter(bool tol_on, bool write_z = true, bool more = false) {
+  // emit: the register-line z-step also stores the spectra of the state it writes into
+  // `yz` (rt.zemit; the caller knows this is the phase's last iteration and nothing
+  // materialises the state after it)
+  ZTests zstep_iter(bool tol_on, bool write_z = true, bool more = false, bool emit = false) {
     const auto* twc = tw.as<cpx<double>>();
     if (rt.z == ZStep::Diag4) {
       HIPCHK(launch_zstep_diag<double>(z.as<double>(), yz.as<double>(), E.as<cpx<double>>(),
@@ -627,6 +630,9 @@ struct Session2D {
       // d-phase, or a materialised state) it stores the z it starts from in `yz`, and the
       // next launch measures that iterate against it (Cmp, one launch late)
       const int mode = zmode == 2 ? 2 : 0;
+      // (a mode-0 launch reads y from `yz`; with a tol test `yz` holds z_old)
+      cpx<double>* Cz = (emit && rt.zemit && !tol_on && mode == 2) ? yz.as<cpx<double>>() : nullptr;
+      cz_valid = Cz != nullptr;
       if (zsplit_ok(tol_on)) {
         if (!zsplit_open) {
           zsp_a = get_event();
@@ -640,12 +646,12 @@ struct Session2D {
         HIPCHK(launch_zline<double>(z.as<double>(), z.as<double>(), z.as<double>(), yz.as<double>(),
                                     W.as<cpx<double>>(), Bhs.as<cpx<double>>(), dws,
                                     dhs.as<cpx<double>>(), sdens.as<double>(), na, K, theta,
-                                    p.rho_z, 2, st, 0, nullptr, nullptr, nullptr));
+                                    p.rho_z, 2, st, 0, nullptr, nullptr, nullptr, Cz));
         HIPCHK(launch_zline<double>(z.as<double>() + zo, z.as<double>() + zo, z.as<double>() + zo,
                                     yz.as<double>() + zo, W.as<cpx<double>>() + wo,
                                     Bhs.as<cpx<double>>() + wo, dws, dhs.as<cpx<double>>(),
                                     sdens.as<double>(), np - na, K, theta, p.rho_z, 2, st3, 0,
-                                    nullptr, nullptr, nullptr));
+                                    nullptr, nullptr, nullptr, Cz ? Cz + na * K * (int64_t)F : nullptr));
         ++zsp_n;
         dws = dhs.as<cpx<double>>();
         return ZTests{};
@@ -661,7 +667,7 @@ struct Session2D {
                                   W.as<cpx<double>>(), Bhs.as<cpx<double>>(),
                                   zmode == 2 ? dws : dhs.as<cpx<double>>(), dhs.as<cpx<double>>(),
                                   sdens.as<double>(), np, K, theta, p.rho_z, mode, st, tolv,
-                                  yz.as<double>(), zpart(), fpart()));
+                                  yz.as<double>(), zpart(), fpart(), Cz));
       zmode = 2;
       dws = dhs.as<cpx<double>>();
       // `yz` holds the z before the current iterate only after a lone Store launch; after a
@@ -707,6 +713,7 @@ struct Session2D {
   // against the z before it (`yz`, ZT_PREV): both slices to natural order in place, then
   // k_zmat with z_old = yz (read before it is overwritten by y)
   void zl_materialize_tol() {
+    cz_valid = false;
     HIPCHK(launch_state_to_nat_inplace<double>(z.as<double>(), np * K, st));
     HIPCHK(launch_state_to_nat_inplace<double>(yz.as<double>(), np * K, st));
     HIPCHK(launch_zmat<double>(z.as<double>(), yz.as<double>(), W.as<cpx<double>>(), dws,
@@ -720,6 +727,7 @@ struct Session2D {
   // its z and `z` its pre-threshold value a = z + y (the launch's state write); the
   // launch's w is dropped.  (z, y) natural <- (yz, z - yz).
   void zl_rollback() {
+    cz_valid = false;
     HIPCHK(launch_state_to_nat_inplace<double>(z.as<double>(), np * K, st));
     HIPCHK(launch_state_to_nat_inplace<double>(yz.as<double>(), np * K, st));
     HIPCHK(launch_sub_inplace<double>(z.as<double>(), yz.as<double>(), np * K * (int64_t)P, st));
@@ -731,6 +739,7 @@ struct Session2D {
   void materialize_z() {
     if (zmode == 0) return;
     zt = ZT_NONE;   // `yz` receives y
+    cz_valid = false;
     if (zmode == 2) {   // state order -> natural a in yz, then (z, y) from it
       HIPCHK(launch_state_to_nat<double>(z.as<double>(), yz.as<double>(), np * K, st));
       HIPCHK(launch_zmat<double>(yz.as<double>(), yz.as<double>(), W.as<cpx<double>>(), dws,
@@ -858,14 +867,19 @@ struct Session2D {
     // ---- D precompute (dP:95-99) ----
     // 110 grid: block j+1's R2C on st3 beside block j's Gram on st (same-box A/B at
     // 8ff8b2a: 949 vs 957.7 ms per C2 step in series, profiles/r03j/preov_ab.txt)
-    const bool ovz = zmode == 2 && st3;
+    // the spectra the last z-launch emitted (rt.zemit): no R2C pass and no st3 hand-off,
+    // k_gram_chol_mf adds the term of w as it stages them
+    const bool zem = cz_valid && zmode == 2 && rt.zemit && rt.dfactor == DFactor::Mfma;
+    const bool ovz = zmode == 2 && st3 && !zem;
     if (ovz) {   // st3's R2C passes read the state the z-phase left on st
       HIPCHK(hipEventRecord(ev_s, st));
       HIPCHK(hipStreamWaitEvent(st3, ev_s, 0));
     }
     for (int64_t jl = 0; jl < nbl; ++jl) {
       cpx<double>* Zc = (ovz && (jl & 1)) ? Zh2.as<cpx<double>>() : Zh.as<cpx<double>>();
-      if (ovz) {   // the same on the lanes (zline.hip), on st3 (see st3)
+      if (zem) {
+        Zc = yz.as<cpx<double>>() + (size_t)jl * ni * K * F;
+      } else if (ovz) {   // the same on the lanes (zline.hip), on st3 (see st3)
         if (jl >= 2) HIPCHK(hipStreamWaitEvent(st3, ev_gz[jl & 1], 0));   // Gram(jl-2) read Zc
         HIPCHK(launch_zhat_line<double>(z.as<double>() + (size_t)jl * ni * K * P,
                                         W.as<cpx<double>>() + (size_t)jl * ni * F, dws, Zc, ni,
@@ -902,7 +916,10 @@ struct Session2D {
             HIPCHK(launch_gram_big(Zc, Bj, Xbig.as<cpx<double>>(), Lj, hj, F, K, ni, p.rho_d, NVg, st));
             break;
           case DFactor::Mfma:
-            HIPCHK(launch_gram_chol_mf(Zc, Bj, Lj, hj, F, K, ni, p.rho_d, NVg, st));
+            HIPCHK(launch_gram_chol_mf(Zc, zem ? Bhs.as<cpx<double>>() + (size_t)jl * ni * F : Bj,
+                                       Lj, hj, F, K, ni, p.rho_d, NVg, st,
+                                       zem ? W.as<cpx<double>>() + (size_t)jl * ni * F : nullptr,
+                                       zem ? dws : nullptr));
             if (dtile) {
               HIPCHK(hipEventRecord(ev_g, st));
               HIPCHK(hipStreamWaitEvent(st2, ev_g, 0));
@@ -1029,10 +1046,13 @@ struct Session2D {
       const bool wz = want_oz || iz + 1 == p.max_it_z;
       // the objective (want_oz) reuses the spectrum buffer between iterations
       const bool more = iz + 1 < p.max_it_z && !want_oz;
+      // tol = 0: the phase's last iteration is known; an objective evaluation after it would
+      // materialise the state over the spectra
+      const bool emit = !tol_on && !want_oz && iz + 1 == p.max_it_z;
       if (zsplit_ok(tol_on))
-        zt_done = zstep_iter(tol_on, wz, more);   // timed as one phase record by zsplit_join
+        zt_done = zstep_iter(tol_on, wz, more, emit);   // timed as one phase record by zsplit_join
       else
-        timed(0, [&] { zt_done = zstep_iter(tol_on, wz, more); });
+        timed(0, [&] { zt_done = zstep_iter(tol_on, wz, more, emit); });
       ++nz;
       if (zt_done.lagged && z_test(iz - 1, zpart(), np) < p.tol) {   // dP:165-167 for iz - 1
         zl_rollback();

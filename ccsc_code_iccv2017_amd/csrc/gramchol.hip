@@ -22,6 +22,7 @@
 // (58 KB) or two column panels (61 KB), so two workgroups share a CU and one's
 // VALU phases (POTRF, TRSM) run beside the other's MFMA phases.
 #include "kernels.hpp"
+#include "zline.hpp"
 
 #include <utility>
 
@@ -297,16 +298,32 @@ __device__ __forceinline__ void fix_diag(int w, int K, int Tn, double rho,
 // HP: right-hand-side entries of h per thread (1 when K NV <= kGcNT: the headline's one);
 // WV: the wave index as a template constant (0..3), or -1 for the run-time index (the
 // TM = 7, HP = 8 shape, whose per-wave instantiations spill)
-template <int TM, int HP, int WV>
+// EM: the code spectra come as the z-step emitted them (k_zline EMIT, zline.hip): Zh is Cz,
+// [ni][K][F] in bin-slot order, twice fft2(u - y) of the state; a staged element becomes
+//   zhat = 1/2 C + XY conj(dhat_k) w_p
+// with the bin's K filter values (ds, [K][F]) and the block's ni w values (Wb, [ni][F];
+// both bin-slot order) held in LDS beside the staging buffers -- what k_zhat_line stores,
+// in its arithmetic.  The term is added in a second pass over the rows a thread has just
+// staged, when its fetch registers are dead (formed in the staging pass itself, beside the
+// seven values in flight, it spills: the kernel sits at the 256-register cap).  Bh is in
+// bin-slot order as well (fz: the workgroup's bin slot); L and h keep the natural bin f.
+// Workgroups take the bins in slot order (k_gram_chol_mf), so that the neighbours on an
+// XCD read neighbouring 16-B elements of the same lines of Zh, Wb, ds and Bh, as they do
+// in natural order with Zh in natural order.
+template <int TM, int HP, int WV, bool EM>
 __device__ __forceinline__ void gram_chol_body(const cpx<double>* __restrict__ Zh,
                                                const cpx<double>* __restrict__ Bh,
                                                cpx<double>* __restrict__ L,
                                                cpx<double>* __restrict__ h, int F, int K, int ni,
-                                               double rho, int NV, int f, char* smem) {
+                                               double rho, int NV, int f, int fz, char* smem,
+                                               const cpx<double>* __restrict__ Wb,
+                                               const cpx<double>* __restrict__ ds) {
   using S = GcShape<TM>;
   constexpr int kGcTW = S::TW, kGcKP = S::KP, kGcLD = S::LD, kGcTM = TM;
   cpx<double>* sA = reinterpret_cast<cpx<double>*>(smem);      // [2][kGcPC][kGcLD]
   cpx<double>* sB = sA + 2 * kGcPC * kGcLD;                    // [2][kGcPC][NV]
+  cpx<double>* sD = sB + 2 * kGcPC * NV;                       // EM: [kGcKP] filter values
+  cpx<double>* sW = sD + kGcKP;                                // EM: [nch kGcPC] w values
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = WV >= 0 ? WV : __builtin_amdgcn_readfirstlane(tid >> 6);
   int Tn = (K + 15) >> 4;
@@ -331,15 +348,17 @@ __device__ __forceinline__ void gram_chol_body(const cpx<double>* __restrict__ Z
       const int idx = tid + i * kGcNT;
       const int pp = idx / kGcKP, k = idx - pp * kGcKP;
       pre[i] = (pp < kGcPC && k < K && p0 + pp < ni)
-                   ? Zh[((int64_t)(p0 + pp) * K + k) * F + f]
+                   ? Zh[((int64_t)(p0 + pp) * K + k) * F + fz]
                    : cpx<double>{0.0, 0.0};
     }
     if (tid < kGcPC * NV) {
       const int pp = tid / NV;
-      preb = (p0 + pp < ni) ? Bh[(int64_t)(p0 * NV + tid) * F + f] : cpx<double>{0.0, 0.0};
+      preb = (p0 + pp < ni) ? Bh[(int64_t)(p0 * NV + tid) * F + fz] : cpx<double>{0.0, 0.0};
     }
   };
-  auto stage = [&](int buf) {
+  // chunk c into staging buffer c & 1
+  auto stage = [&](int c) {
+    const int buf = c & 1;
     cpx<double>* a = sA + buf * kGcPC * kGcLD;
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
@@ -348,9 +367,40 @@ __device__ __forceinline__ void gram_chol_body(const cpx<double>* __restrict__ Z
       if (pp < kGcPC) a[pp * kGcLD + k] = pre[i];
     }
     if (tid < kGcPC * NV) sB[buf * kGcPC * NV + tid] = preb;
+    if constexpr (EM) {
+      // each thread's own elements again (no barrier); the compiler must not forward the
+      // stored values and so keep the fetch registers alive through this pass
+      asm volatile("" ::: "memory");
+      const cpx<double>* w = sW + c * kGcPC;
+      const double sc = (double)zl::P;
+      // an opaque copy of the thread index: the pass's LDS addresses are formed here, not
+      // hoisted out of the chunk loop into registers held across the MFMAs
+      int t = tid;
+      asm volatile("" : "+v"(t));
+#pragma unroll
+      for (int i = 0; i < kPer; ++i) {
+        const int idx = t + i * kGcNT;
+        const int pp = idx / kGcKP, k = idx - pp * kGcKP;
+        if (pp < kGcPC) {   // k_zhat_line's store expression (zline.hip)
+          const cpx<double> cb = a[pp * kGcLD + k];
+          const cpx<double> q = cmulc(sD[k], w[pp]);
+          a[pp * kGcLD + k] = {fma(0.5, cb.x, sc * q.x), fma(0.5, cb.y, sc * q.y)};
+        }
+      }
+    }
   };
   const int nch = (ni + kGcPC - 1) / kGcPC;
+  if constexpr (EM) {
+    // the bin's filter values and the block's w, zero past K and past the last patch so
+    // that the padding columns and rows stay zero (ahead of chunk 0's loads: beside them
+    // in flight these loops spill)
+    for (int k = tid; k < kGcKP; k += kGcNT)
+      sD[k] = k < K ? ds[(int64_t)k * F + fz] : cpx<double>{0.0, 0.0};
+    for (int q = tid; q < nch * kGcPC; q += kGcNT)
+      sW[q] = q < ni ? Wb[(int64_t)q * F + fz] : cpx<double>{0.0, 0.0};
+  }
   fetch(0);
+  if constexpr (EM) __syncthreads();
   stage(0);
   __syncthreads();
   for (int c = 0; c < nch; ++c) {
@@ -381,7 +431,7 @@ __device__ __forceinline__ void gram_chol_body(const cpx<double>* __restrict__ Z
           hacc[i] = cmacc(hacc[i], a[pp * kGcLD + k], b[pp * NV + uv]);
       }
     }
-    if (c + 1 < nch) stage(buf ^ 1);
+    if (c + 1 < nch) stage(c + 1);
     __syncthreads();
   }
 #pragma unroll
@@ -463,25 +513,28 @@ __device__ __forceinline__ void gram_chol_body(const cpx<double>* __restrict__ Z
   }
 }
 
-template <int TM, int HP>
+template <int TM, int HP, bool EM>
 __global__ __launch_bounds__(kGcNT, GcShape<TM>::WGS) void k_gram_chol_mf(const cpx<double>* __restrict__ Zh,
                                                            const cpx<double>* __restrict__ Bh,
                                                            cpx<double>* __restrict__ L,
                                                            cpx<double>* __restrict__ h, int F,
-                                                           int K, int ni, double rho, int NV) {
+                                                           int K, int ni, double rho, int NV,
+                                                           const cpx<double>* __restrict__ Wb,
+                                                           const cpx<double>* __restrict__ ds) {
   const int per = gridDim.x >> 3;
-  const int f = (blockIdx.x & 7) * per + (blockIdx.x >> 3);   // XCD-aware: neighbours share L2
-  if (f >= F) return;
+  const int fz = (blockIdx.x & 7) * per + (blockIdx.x >> 3);   // XCD-aware: neighbours share L2
+  if (fz >= F) return;
+  const int f = EM ? zl::slot_bin(fz) : fz;   // EM: bin slots in turn, fz the bin in the inputs' order
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if constexpr (TM == 7 && HP > 1) {
-    gram_chol_body<TM, HP, -1>(Zh, Bh, L, h, F, K, ni, rho, NV, f, smem);
+    gram_chol_body<TM, HP, -1, EM>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds);
   } else {
     // every wave runs the same barriers in its own instantiation
     switch (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6)) {
-      case 0: gram_chol_body<TM, HP, 0>(Zh, Bh, L, h, F, K, ni, rho, NV, f, smem); break;
-      case 1: gram_chol_body<TM, HP, 1>(Zh, Bh, L, h, F, K, ni, rho, NV, f, smem); break;
-      case 2: gram_chol_body<TM, HP, 2>(Zh, Bh, L, h, F, K, ni, rho, NV, f, smem); break;
-      default: gram_chol_body<TM, HP, 3>(Zh, Bh, L, h, F, K, ni, rho, NV, f, smem); break;
+      case 0: gram_chol_body<TM, HP, 0, EM>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds); break;
+      case 1: gram_chol_body<TM, HP, 1, EM>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds); break;
+      case 2: gram_chol_body<TM, HP, 2, EM>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds); break;
+      default: gram_chol_body<TM, HP, 3, EM>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds); break;
     }
   }
 }
@@ -491,10 +544,20 @@ static int gc_tm(int K) { const int t = (K + 15) / 16; return t <= 7 ? 7 : t <= 
 bool gram_chol_mf_ok(int K, int NV) {
   return K <= 16 * kGcMaxTM && K * NV <= kGcHPT * kGcNT && NV <= 16;
 }
+size_t gram_chol_mf_smem(int NV, int K, int ni);
+static size_t gc_lds_cap(int K) { return (size_t)(gc_tm(K) <= 7 ? 80 : 160) * 1024; }
+// the emitted form keeps the block's w in LDS: the block must leave the CU's LDS to as many
+// workgroups as the kernel runs there
+bool gram_chol_mf_emit_ok(int K, int NV, int ni) {
+  return gram_chol_mf_ok(K, NV) && ni > 0 && gram_chol_mf_smem(NV, K, ni) <= gc_lds_cap(K);
+}
 
-size_t gram_chol_mf_smem(int NV, int K) {
+// ni > 0: the staging form of the emitted spectra, which also holds the bin's filter values
+// and the block's ni w values (whole chunks)
+size_t gram_chol_mf_smem(int NV, int K, int ni) {
   const int tm = gc_tm(K);
-  const size_t stage = (size_t)2 * kGcPC * (16 * tm + 1) * 16 + (size_t)2 * kGcPC * NV * 16;
+  const size_t stage = (size_t)2 * kGcPC * (16 * tm + 1) * 16 + (size_t)2 * kGcPC * NV * 16 +
+                       (ni > 0 ? (size_t)(16 * tm + (ni + kGcPC - 1) / kGcPC * kGcPC) * 16 : 0);
   const size_t chol = (size_t)2 * tm * kGcTSZ * 16;   // two column panels
   return stage > chol ? stage : chol;
 }
@@ -502,24 +565,31 @@ size_t gram_chol_mf_smem(int NV, int K) {
 template <int TM, int HP>
 static void gram_chol_mf_go(const cpx<double>* Zh, const cpx<double>* Bh, cpx<double>* L,
                             cpx<double>* h, int F, int K, int ni, double rho, int NV,
-                            hipStream_t st) {
+                            hipStream_t st, const cpx<double>* Wb, const cpx<double>* ds) {
   const int grid = ((F + 7) / 8) * 8;
-  hipLaunchKernelGGL((k_gram_chol_mf<TM, HP>), dim3(grid), dim3(kGcNT), gram_chol_mf_smem(NV, K), st,
-                     Zh, Bh, L, h, F, K, ni, rho, NV);
+  if (Wb)
+    hipLaunchKernelGGL((k_gram_chol_mf<TM, HP, true>), dim3(grid), dim3(kGcNT),
+                       gram_chol_mf_smem(NV, K, ni), st, Zh, Bh, L, h, F, K, ni, rho, NV, Wb, ds);
+  else
+    hipLaunchKernelGGL((k_gram_chol_mf<TM, HP, false>), dim3(grid), dim3(kGcNT),
+                       gram_chol_mf_smem(NV, K, 0), st, Zh, Bh, L, h, F, K, ni, rho, NV, Wb, ds);
 }
 
 hipError_t launch_gram_chol_mf(const cpx<double>* Zh, const cpx<double>* Bh, cpx<double>* L,
                                cpx<double>* h, int F, int K, int ni, double rho, int NV,
-                               hipStream_t st) {
+                               hipStream_t st, const cpx<double>* Wb, const cpx<double>* ds) {
   if (!gram_chol_mf_ok(K, NV)) return hipErrorInvalidValue;
+  // the emitted form reads bin slots of the 110 x 110 grid's half spectrum
+  if ((Wb != nullptr) != (ds != nullptr)) return hipErrorInvalidValue;
+  if (Wb && (F != zl::F || NV != 1 || !gram_chol_mf_emit_ok(K, NV, ni))) return hipErrorInvalidValue;
   switch (gc_tm(K)) {
     case 7:
-      if (K * NV <= kGcNT) gram_chol_mf_go<7, 1>(Zh, Bh, L, h, F, K, ni, rho, NV, st);
-      else gram_chol_mf_go<7, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st);
+      if (K * NV <= kGcNT) gram_chol_mf_go<7, 1>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds);
+      else gram_chol_mf_go<7, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds);
       break;
-    case 8: gram_chol_mf_go<8, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st); break;
-    case 10: gram_chol_mf_go<10, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st); break;
-    default: gram_chol_mf_go<12, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st); break;
+    case 8: gram_chol_mf_go<8, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds); break;
+    case 10: gram_chol_mf_go<10, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds); break;
+    default: gram_chol_mf_go<12, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds); break;
   }
   return hipGetLastError();
 }

@@ -75,11 +75,14 @@ size_t zline_smem_bytes();
 // patch sums of ||z - Zt||^2, ||z||^2 -> zpart[2p..2p+1]; Form: the patch sums of
 // ||z_new - z||^2, ||z_new||^2 of the produced iterate -> fpart[2p..2p+1] (needs
 // dcorr == dhat); mode 3 = finalize (Store | Cmp, no advance).
+// Cz (mode 2, tol 0 only): the launch also stores fft2(u - y) of the state it writes,
+// unscaled (twice the spectrum), as [npatch][K][F] half spectra in bin-slot order.
 template <typename T>
 hipError_t launch_zline(const T* A, T* Ao, const T* Zn, const T* Yn, cpx<T>* W, const cpx<T>* Bs,
                         const cpx<T>* dcorr, const cpx<T>* dhat, const T* sden, int64_t npatch,
                         int K, T theta, T rho, int mode, hipStream_t st, int tol = 0,
-                        T* Zt = nullptr, T* zpart = nullptr, T* fpart = nullptr);
+                        T* Zt = nullptr, T* zpart = nullptr, T* fpart = nullptr,
+                        cpx<T>* Cz = nullptr);
 // tol bits of launch_zline (zline.hip): store z_cur / compare with the stored z / the
 // Parseval test of the produced iterate
 constexpr int kZlTolStore = 1, kZlTolCmp = 2, kZlTolForm = 4;
@@ -106,10 +109,17 @@ hipError_t launch_gram_chol(const cpx<T>* Zh, const cpx<T>* Bh, cpx<T>* L, cpx<T
                             int K, int ni, T rho, int NV, hipStream_t st);
 // The same outputs on the matrix cores (gramchol.hip): fp64 MFMA Gram and blocked
 // Cholesky, K <= 112, K * NV <= 2048.
+// With Wb and ds (the 110 x 110 grid only): Zh is what launch_zline's Cz received for the
+// block, [ni][K][F] in bin-slot order; the kernel forms zhat = Zh / 2 + XY conj(ds_k) Wb_p
+// per bin as it stages the rows (Wb [ni][F] the block's w, ds [K][F] the filter spectrum w
+// was solved with, both in bin-slot order).  Bh is then B^ in bin-slot order too (one view);
+// L and h stay in natural bin order.
 bool gram_chol_mf_ok(int K, int NV);
+bool gram_chol_mf_emit_ok(int K, int NV, int ni);   // the Wb / ds form (the block's w fits the LDS)
 hipError_t launch_gram_chol_mf(const cpx<double>* Zh, const cpx<double>* Bh, cpx<double>* L,
                                cpx<double>* h, int F, int K, int ni, double rho, int NV,
-                               hipStream_t st);
+                               hipStream_t st, const cpx<double>* Wb = nullptr,
+                               const cpx<double>* ds = nullptr);
 // The same outputs for 192 < K <= 400 (gramchol_big.hip): the block's code spectra
 // transposed into X ([F][ni][K], ni K F complex of workspace), the Gram on the matrix
 // cores into the packed slots of L, then a left-looking Cholesky in place.

@@ -378,6 +378,13 @@ void resolve_problem(ccsc_problem& p) {
     if (p.sb[i] + 2 * r < p.psf) throw Err(CCSC_E_INVALID, "grid smaller than the filter");
 }
 
+bool objective_refresh(const ccsc_problem& p) {
+  if (p.variant == CCSC_DPAR) return p.verbose == CCSC_VERBOSE_BRIEF;  // dP:126,161
+  if (p.variant == CCSC_L4D) return p.verbose == CCSC_VERBOSE_ALL;     // L4:135,170
+  if (p.variant == CCSC_L3D) return p.verbose == CCSC_VERBOSE_ALL;     // L3:145,185
+  return p.verbose != CCSC_VERBOSE_NONE;                               // dZ:127,165
+}
+
 void check_supported(const ccsc_problem& p, Geom* Gout) {
   // (right-hand sides past the Gram kernels' budget, K * views > 2048 or views > 16, are
   // formed by the per-bin GEMM of hs23.hip instead, Route::h_sep)
@@ -482,6 +489,12 @@ Route route2d(const ccsc_problem& p, const Geom& g, int rank, int nranks, bool r
     if (rt.dfactor == DFactor::Mfma && dsolve_tile_ok(K, NV) && env_on("CCSC_DS_TILE"))
       rt.dsolve = DSolve::Tile;
     rt.st2 = rt.dsolve == DSolve::Tile;
+    // tol = 0 fixes the last z-iteration of a phase in advance; only k_gram_chol_mf reads
+    // the emitted spectra (every other factor keeps k_zhat_line); a run that evaluates the
+    // objective after every z-iteration materialises the state before any precompute
+    rt.zemit = rt.z == ZStep::Line && !(p.tol > 0) && rt.dfactor == DFactor::Mfma && !rt.h_sep &&
+               !objective_refresh(p) && !p.trace_objective && gram_chol_mf_emit_ok(K, NV, ni) &&
+               env_on("CCSC_ZEMIT");
   }
   if (rt.z == ZStep::Planes3) {
     // fused t-FFT + z-solve (k_tsolve3): TC x' columns per workgroup; C4 (74x74x42,
@@ -573,6 +586,8 @@ std::vector<BufRow> mem_plan2d(const ccsc_problem& p, const Geom& g, const Route
   set(b2::b, np * NV * (size_t)p.sb[0] * p.sb[1] * (is3 ? (size_t)p.sb[2] : 1) * R);
   set(b2::Bhat, np * NV * F * C);
   for (int i : {b2::z, b2::yz}) set(i, np * K * P * R);
+  // the emitted half spectra (F complex per slice, 1.8% more than its P reals) share `yz`
+  if (rt.zemit) set(b2::yz, std::max(np * K * P * R, np * K * F * C));
   // 2D split z-state (zsplit.hip): w per patch + the filter spectrum it was solved with;
   // with tol > 0 a buffer so z_old survives for the tol test (the 4D and 3D z-steps
   // compare per slice/plane; the register-line z-step keeps z_old in the y buffer)

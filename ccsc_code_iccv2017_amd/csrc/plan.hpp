@@ -55,6 +55,9 @@ int plan_lines(int X, int Y, int Tn, bool with_t, LinePlan& lp);
 
 // ---- problems -------------------------------------------------------------------------
 void resolve_problem(ccsc_problem& p);   // defaults and validation (Appendix A of SURVEY.md)
+// the consensus learners refresh the objective after every d- / z-iteration (the reference's
+// verbose rules are the same for both phases)
+bool objective_refresh(const ccsc_problem& p);
 
 // Transform geometry of one slice: the (x, y) plane grid and, for the 3D
 // learner, the t-direction tile (Tn = 1 otherwise).
@@ -114,6 +117,13 @@ struct Route {
   // switches, read once: CCSC_WB_STAGE (0 keeps k_dsolve_wbv), CCSC_ZSPLIT2 (0 keeps the
   // z-phase on one stream); CCSC_DS_TILE=0 (the two-sweep k_dsolve) is folded into dsolve
   bool wb_stage = true, zsplit2 = true;
+  // register-line z-step, tol = 0, MFMA factor, no objective evaluation after the
+  // z-iterations (verbose refresh or trace_objective: it materialises the state over `yz`,
+  // so the spectra would never be read and the larger buffer would buy nothing): the last
+  // z-iteration of a phase also stores the code spectra it forms into `yz` (idle in that
+  // route) and the next D-precompute's Gram reads them instead of a k_zhat_line pass;
+  // CCSC_ZEMIT=0 keeps that pass
+  bool zemit = false;
 };
 // consensus learners (dP, dZ, 3D, 4D) / the 2-3D learner; the problem resolved, g from
 // check_supported.  route_hs throws for several ranks past K = 192.

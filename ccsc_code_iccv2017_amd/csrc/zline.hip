@@ -347,8 +347,14 @@ __device__ __forceinline__ int fresh(int v) {
 //           §4).
 // MODE 3 ("finalize"): kZtStore | kZtCmp without advancing: no state write, no R2C, W
 // untouched.
+// EMIT (MODE 2, TOL 0): P9 also stores the bins C_k it forms -- fft2(u - y) of the state the
+// launch has just written, unscaled (twice the spectrum, the separation's factor) -- to
+// Cz[(p K + k) F + slot] in bin-slot order, for the D-precompute's Gram (gramchol.hip), which
+// adds the correction term conj(dhat_k) w of the w stored at the launch's end.  Cz travels
+// in the Zt argument, which TOL 0 leaves unused, so the plain instantiations keep their
+// kernel arguments and their code.
 constexpr int kZtStore = kZlTolStore, kZtCmp = kZlTolCmp, kZtForm = kZlTolForm;
-template <typename T, int MODE, int TOL>
+template <typename T, int MODE, int TOL, bool EMIT = false>
 __global__ __launch_bounds__(zl::NT) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_zline(const T* A, T* Ao, const T* Zn, const T* Yn,
                                                   cpx<T>* __restrict__ W,
                                                   const cpx<T>* __restrict__ Bs,
@@ -358,6 +364,7 @@ __global__ __launch_bounds__(zl::NT) __attribute__((amdgpu_waves_per_eu(3, 3))) 
                                                   T rho, T* Zt, T* __restrict__ zpart,
                                                   T* __restrict__ fpart) {
   static_assert(MODE == 0 || MODE == 2 || MODE == 3, "zline mode");
+  static_assert(!EMIT || (MODE == 2 && TOL == 0), "the emitting z-step is mode 2 without a tol test");
   static_assert(TOL >= 0 && TOL <= 7 && (!(TOL & kZtCmp) || (TOL & kZtStore)) &&
                     (MODE != 0 || TOL <= kZtStore) &&
                     (MODE != 3 || TOL == (kZtStore | kZtCmp)),
@@ -612,8 +619,11 @@ __global__ __launch_bounds__(zl::NT) __attribute__((amdgpu_waves_per_eu(3, 3))) 
         const int s9 = fresh(sb);
         const cpx<T>* dk = dhat + (int64_t)k * zl::F;
         const uint32_t bo = (uint32_t)(c * 11 + s9) * 16u;
+        // EMIT: the slice's spectrum, 16-B nontemporal stores at the fld's addressing
+        cpx<T>* ck = EMIT ? reinterpret_cast<cpx<T>*>(Zt) + (p * K + k) * zl::F : nullptr;
         fwd_line_r<T, true>(col, yr, yw, [&](int k1, cpx<T> cb) {
           acc[k1] = cmac(acc[k1], fld<cpx<T>>(dk, bo, k1 * 616 * 16), cb);
+          if constexpr (EMIT) sst2<cpx<T>>(ck, bo, k1 * 616 * 16, cb);
         });
       }
     }
@@ -800,11 +810,11 @@ __global__ __launch_bounds__(1024) void k_state_to_nat_inplace(T* a) {
 
 bool zline_grid(const Grid2D& G) { return grid_is<Grid110>(G); }
 
-template <typename T, int MODE, int TOL>
+template <typename T, int MODE, int TOL, bool EMIT = false>
 static void zline_go(hipStream_t st, int64_t npatch, const T* A, T* Ao, const T* Zn, const T* Yn,
                      cpx<T>* W, const cpx<T>* Bs, const cpx<T>* dcorr, const cpx<T>* dhat,
                      const T* sden, int K, T theta, T rho, T* Zt, T* zpart, T* fpart) {
-  hipLaunchKernelGGL((k_zline<T, MODE, TOL>), dim3((unsigned)npatch), dim3(zl::NT), kZlSmem, st,
+  hipLaunchKernelGGL((k_zline<T, MODE, TOL, EMIT>), dim3((unsigned)npatch), dim3(zl::NT), kZlSmem, st,
                      A, Ao, Zn, Yn, W, Bs, dcorr, dhat, sden, K, theta, rho, Zt, zpart, fpart);
 }
 
@@ -812,8 +822,14 @@ template <typename T>
 hipError_t launch_zline(const T* A, T* Ao, const T* Zn, const T* Yn, cpx<T>* W, const cpx<T>* Bs,
                         const cpx<T>* dcorr, const cpx<T>* dhat, const T* sden, int64_t npatch,
                         int K, T theta, T rho, int mode, hipStream_t st, int tol, T* Zt,
-                        T* zpart, T* fpart) {
+                        T* zpart, T* fpart, cpx<T>* Cz) {
   if (npatch <= 0) return hipSuccess;
+  if (Cz) {   // the emitting z-step: mode 2, no tol test
+    if (mode != 2 || tol != 0) return hipErrorInvalidValue;
+    zline_go<T, 2, 0, true>(st, npatch, A, Ao, Zn, Yn, W, Bs, dcorr, dhat, sden, K, theta, rho,
+                            reinterpret_cast<T*>(Cz), zpart, fpart);
+    return hipGetLastError();
+  }
   if ((tol & kZtStore) && !Zt) return hipErrorInvalidValue;
   if ((tol & kZtCmp) && !zpart) return hipErrorInvalidValue;
   if ((tol & kZtForm) && (!fpart || dcorr != dhat)) return hipErrorInvalidValue;
@@ -882,7 +898,7 @@ template hipError_t launch_zline<double>(const double*, double*, const double*, 
                                          cpx<double>*, const cpx<double>*, const cpx<double>*,
                                          const cpx<double>*, const double*, int64_t, int, double,
                                          double, int, hipStream_t, int, double*, double*,
-                                         double*);
+                                         double*, cpx<double>*);
 template hipError_t launch_zhat_line<double>(const double*, const cpx<double>*,
                                              const cpx<double>*, cpx<double>*, int64_t, int,
                                              double, hipStream_t);

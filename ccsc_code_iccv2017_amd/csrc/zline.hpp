@@ -27,6 +27,11 @@ __host__ __device__ constexpr int bin_slot(int f) {
   const int y = f / Xh, c = f - y * Xh;
   return (y % 10) * 616 + c * 11 + (y % 11);
 }
+// the bin f = y*Xh + c that sits in bin slot s (bin_slot's inverse)
+__host__ __device__ constexpr int slot_bin(int s) {
+  const int k1 = s / 616, r = s - k1 * 616, c = r / 11, k2 = r - c * 11;
+  return elem_b(k2, k1) * Xh + c;
+}
 // pixel e = y*110 + x of a slice -> its offset in state order: pair n2*550 + (y>>1)*10 + n1
 // (layout A of row pair y>>1: lane n1, register n2), row parity in the pair
 __host__ __device__ constexpr int state_off(int e) {
