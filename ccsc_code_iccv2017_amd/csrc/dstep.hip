@@ -608,11 +608,6 @@ __device__ __forceinline__ void row16_sum4_store(const cpx<double> (&p)[4], int 
   w3 += dpp_mov<0xB1>(w3);                 // quad_perm [1,0,3,2]
   if ((r & 1) == 0) reinterpret_cast<double*>(out)[r >> 1] = w3;
 }
-__device__ __forceinline__ void wave_sync_lds() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // NV right-hand sides per (block, f) -- the 4D views, L23's W wavelengths -- are solved one
 // after the other against the factor tiles the workgroup loaded once (k_dsolve streams the
 // factor twice per group of up to 8 right-hand sides); layouts [blk][k][uv][F] (Ch, Dh) and
@@ -780,44 +775,25 @@ hipError_t launch_dsolve_tile(const cpx<double>* L, const cpx<double>* h, const 
 
 // In place: the diagonal 16 x 16 tiles of one block's F packed factors <- their
 // inverses (the form k_dsolve_tile reads), once per precompute.  One wave per
-// (f, tile J) item: L_JJ staged in LDS, lane c & 15 forms column c of M = L_JJ^-1 by
-// forward substitution into the wave's LDS copy of M (each lane reads back only its
-// own column; the four lanes of a column write the same values):
-//   M[r][c] = (delta_rc - sum_{k<r} L[r][k] M[k][c]) / L[r][r],
-// a row's 2r broadcast reads issued together.
+// (f, tile J) item: L_JJ staged in LDS (diag_tile_elem), then inverted and stored by
+// diag_tile_invert (kernels.hpp, shared with k_gram_chol_mf's fused form).
 __global__ __launch_bounds__(256) void k_invert_diag(cpx<double>* __restrict__ L, int F, int K,
                                                      int Tn) {
-  __shared__ cpx<double> sL[4][16 * 17], sM[4][16 * 17];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15;
+  __shared__ cpx<double> sL[4][kDiTSZ], sM[4][kDiTSZ];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t item = (int64_t)blockIdx.x * 4 + wave;   // f * Tn + J
   if (item >= (int64_t)F * Tn) return;                   // wave-uniform
-  const int f = (int)(item / Tn), J = (int)(item - (int64_t)f * Tn);
-  cpx<double>* Lf = L + (int64_t)f * (K * (K + 1) / 2);
+  const int64_t f = item / Tn;
+  const int J = (int)(item - f * Tn);
+  cpx<double>* Lf = L + f * (K * (K + 1) / 2);
   cpx<double>* Lw = sL[wave];
-  cpx<double>* Mw = sM[wave];
   for (int e = lane; e < 256; e += 64) {
     const int r = e & 15, cc = e >> 4, R = 16 * J + r, C = 16 * J + cc;
-    Lw[cc * 17 + r] = (r >= cc && R < K) ? Lf[C * K - (C * (C - 1)) / 2 + R - C]
-                                         : cpx<double>{(r == cc) ? 1.0 : 0.0, 0.0};
+    Lw[cc * kDiTS + r] =
+        diag_tile_elem(J, r, cc, K, [&] { return Lf[C * K - (C * (C - 1)) / 2 + R - C]; });
   }
   wave_sync_lds();
-  for (int r = 0; r < 16; ++r) {
-    cpx<double> s0 = {(r == c) ? 1.0 : 0.0, 0.0}, s1 = {0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < 15; ++k) {
-      if (k < r) {
-        const cpx<double> p = cmul(Lw[k * 17 + r], Mw[k * 17 + c]);
-        if (k & 1) s1 = csub(s1, p);
-        else s0 = csub(s0, p);
-      }
-    }
-    Mw[r * 17 + c] = cscale(cadd(s0, s1), 1.0 / Lw[r * 17 + r].x);
-  }
-  if (lane < 16) {
-    const int C = 16 * J + c;
-    for (int r = c; r < 16 && 16 * J + r < K; ++r)
-      Lf[C * K - (C * (C - 1)) / 2 + 16 * J + r - C] = Mw[r * 17 + c];
-  }
+  diag_tile_invert(Lw, sM[wave], Lf, J, K, lane);
 }
 
 hipError_t launch_invert_diag(cpx<double>* L, int F, int K, hipStream_t st) {

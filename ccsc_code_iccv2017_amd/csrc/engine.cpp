@@ -292,11 +292,13 @@ struct Session2D {
 
   // profiling
   bool prof = false;
-  struct Rec { int id; hipEvent_t a, b; int n = 1; };   // n launches between a and b
+  struct Rec { int id; hipEvent_t a, b; int n = 1; int64_t blocks = 1; };   // n launches between a and b
   std::vector<Rec> recs;
   std::vector<hipEvent_t> pool;
   int64_t k_launch[5] = {0, 0, 0, 0, 0};
   double k_ms[5] = {0, 0, 0, 0, 0};
+  // blocks the launches of id 1 covered (one per block launch, nbl per grouped launch)
+  int64_t k_blocks1 = 0;
 
   hipEvent_t get_event() {
     if (!pool.empty()) {
@@ -309,12 +311,12 @@ struct Session2D {
     return e;
   }
   template <typename Fn>
-  void timed(int id, Fn&& fn) {
+  void timed(int id, Fn&& fn, int64_t blocks = 1) {
     if (!prof) {
       fn();
       return;
     }
-    Rec rc{id, get_event(), get_event()};
+    Rec rc{id, get_event(), get_event(), 1, blocks};
     HIPCHK(hipEventRecord(rc.a, st));
     fn();
     HIPCHK(hipEventRecord(rc.b, st));
@@ -326,6 +328,7 @@ struct Session2D {
       HIPCHK(hipEventSynchronize(rc.b));
       HIPCHK(hipEventElapsedTime(&ms, rc.a, rc.b));
       k_launch[rc.id] += rc.n;
+      if (rc.id == 1) k_blocks1 += rc.blocks;
       k_ms[rc.id] += ms;
       pool.push_back(rc.a);
       pool.push_back(rc.b);
@@ -871,11 +874,25 @@ struct Session2D {
     // k_gram_chol_mf adds the term of w as it stages them
     const bool zem = cz_valid && zmode == 2 && rt.zemit && rt.dfactor == DFactor::Mfma;
     const bool ovz = zmode == 2 && st3 && !zem;
+    // k_gram_chol_mf leaves the inverted diagonal tiles itself (rt.dinv): no k_invert_diag
+    const bool dinv = dtile && rt.dinv && rt.dfactor == DFactor::Mfma;
+    const bool dgrp = zem && rt.dgroup;
+    if (dgrp) {
+      // every local block's spectra lie in `yz`: one launch over them (its partial last
+      // round of workgroups paid once, not per block)
+      timed(1, [&] {
+        HIPCHK(launch_gram_chol_mf(yz.as<cpx<double>>(), Bhs.as<cpx<double>>(),
+                                   L.as<cpx<double>>(), h.as<cpx<double>>(), F, K, ni, p.rho_d,
+                                   NV, st, W.as<cpx<double>>(), dws, (int)nbl, dinv));
+        // (a block too large for the fused form's LDS: L is contiguous over the blocks)
+        if (dtile && !dinv) HIPCHK(launch_invert_diag(L.as<cpx<double>>(), (int)nbl * F, K, st));
+      }, nbl);
+    }
     if (ovz) {   // st3's R2C passes read the state the z-phase left on st
       HIPCHK(hipEventRecord(ev_s, st));
       HIPCHK(hipStreamWaitEvent(st3, ev_s, 0));
     }
-    for (int64_t jl = 0; jl < nbl; ++jl) {
+    for (int64_t jl = 0; jl < (dgrp ? 0 : nbl); ++jl) {
       cpx<double>* Zc = (ovz && (jl & 1)) ? Zh2.as<cpx<double>>() : Zh.as<cpx<double>>();
       if (zem) {
         Zc = yz.as<cpx<double>>() + (size_t)jl * ni * K * F;
@@ -919,8 +936,8 @@ struct Session2D {
             HIPCHK(launch_gram_chol_mf(Zc, zem ? Bhs.as<cpx<double>>() + (size_t)jl * ni * F : Bj,
                                        Lj, hj, F, K, ni, p.rho_d, NVg, st,
                                        zem ? W.as<cpx<double>>() + (size_t)jl * ni * F : nullptr,
-                                       zem ? dws : nullptr));
-            if (dtile) {
+                                       zem ? dws : nullptr, 1, dinv));
+            if (dtile && !dinv) {
               HIPCHK(hipEventRecord(ev_g, st));
               HIPCHK(hipStreamWaitEvent(st2, ev_g, 0));
               HIPCHK(launch_invert_diag(Lj, F, K, st2));
@@ -933,7 +950,7 @@ struct Session2D {
       });
       if (ovz) HIPCHK(hipEventRecord(ev_gz[jl & 1], st));
     }
-    if (dtile) {   // every block's inverted diagonal tiles before the first d-solve
+    if (dtile && !dinv && !dgrp) {   // every block's inverted diagonal tiles before the first d-solve
       HIPCHK(hipEventRecord(ev_i, st2));
       HIPCHK(hipStreamWaitEvent(st, ev_i, 0));
     }
@@ -1142,8 +1159,10 @@ struct Session2D {
       case 0:  // z-iteration, SURVEY.md §8(d): n K (4 s P + 4 c F) + n c F V  (s = 8, c = 16):
                // prox+dual+R2C, solve, C2R stages each reading/writing their operands once
         return (double)np * Kd * (4.0 * 8.0 * Pd + 4.0 * 16.0 * Fd) + (double)np * NV * 16.0 * Fd;
-      case 1:  // gram+chol per block: read A (ni x K x F) + b, write L, h
-        return (double)ni * Kd * Fd * 16.0 + ni * Fd * 16.0 + Fd * Kp * 16.0 + Fd * Kd * 16.0;
+      case 1:  // gram+chol per block: read A (ni x K x F) + b, write L, h; a launch covers
+               // one block or, grouped (rt.dgroup), the rank's: the mean over the launches timed
+        return ((double)ni * Kd * Fd * 16.0 + ni * Fd * 16.0 + Fd * Kp * 16.0 + Fd * Kd * 16.0) *
+               (k_launch[1] ? (double)k_blocks1 / (double)k_launch[1] : 1.0);
       case 2:  // dsolve over local blocks: read L, h, C; write Dhat
         return (double)nbl * Fd * (Kp + 3.0 * Kd) * 16.0;
       case 3:  // dual+R2C: read D, y; write y, C

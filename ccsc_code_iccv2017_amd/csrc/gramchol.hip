@@ -310,14 +310,23 @@ __device__ __forceinline__ void fix_diag(int w, int K, int Tn, double rho,
 // Workgroups take the bins in slot order (k_gram_chol_mf), so that the neighbours on an
 // XCD read neighbouring 16-B elements of the same lines of Zh, Wb, ds and Bh, as they do
 // in natural order with Zh in natural order.
-template <int TM, int HP, int WV, bool EM>
+// DI (TM = 7, per-wave instantiations): the kernel leaves the inverted diagonal tiles itself,
+// the form k_dsolve_tile reads (k_invert_diag's output).  Wave 0's diagonal lanes put L_jj,
+// staged by k_invert_diag's rule, into one of two LDS tiles at the end of panel sweep j
+// instead of storing it; wave 3, which holds no panel rows at Tn <= 7, inverts tile j - 1
+// during sweep j (after its trailing-update tiles of step j - 1) and the last tile after the
+// loop, through diag_tile_invert (kernels.hpp).  sDi: [2][kDiTSZ] L tiles + [kDiTSZ] M, past
+// the staging buffers and the panels.
+template <int TM, int HP, int WV, bool EM, bool DI>
 __device__ __forceinline__ void gram_chol_body(const cpx<double>* __restrict__ Zh,
                                                const cpx<double>* __restrict__ Bh,
                                                cpx<double>* __restrict__ L,
                                                cpx<double>* __restrict__ h, int F, int K, int ni,
                                                double rho, int NV, int f, int fz, char* smem,
                                                const cpx<double>* __restrict__ Wb,
-                                               const cpx<double>* __restrict__ ds) {
+                                               const cpx<double>* __restrict__ ds, int dioff) {
+  static_assert(!DI || (TM == 7 && WV >= 0), "fused inversion: wave 3 is free of panel rows");
+  static_assert(kDiTS == kGcTS, "one LDS tile layout");
   using S = GcShape<TM>;
   constexpr int kGcTW = S::TW, kGcKP = S::KP, kGcLD = S::LD, kGcTM = TM;
   cpx<double>* sA = reinterpret_cast<cpx<double>*>(smem);      // [2][kGcPC][kGcLD]
@@ -493,7 +502,15 @@ __device__ __forceinline__ void gram_chol_body(const cpx<double>* __restrict__ Z
         }
       }
       const int gr_ = 16 * ti + row;
-      if (mine && (!diag || wave == 0) && gr_ < K) {
+      if constexpr (DI) {
+        if (diag && wave == 0) {   // L_jj for wave 3, not to HBM: its slots receive L_jj^-1
+          cpx<double>* Dj = reinterpret_cast<cpx<double>*>(smem + dioff) + (j & 1) * kDiTSZ;
+#pragma unroll
+          for (int c = 0; c < 16; ++c)
+            Dj[c * kDiTS + row] = diag_tile_elem(j, row, c, K, [&] { return x[c]; });
+        }
+      }
+      if (mine && (DI ? !diag : (!diag || wave == 0)) && gr_ < K) {
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
           const int gc = 16 * j + c;
@@ -505,36 +522,59 @@ __device__ __forceinline__ void gram_chol_body(const cpx<double>* __restrict__ Z
         for (int c = 0; c < 16; ++c) P[ti * kGcTSZ + c * kGcTS + row] = x[c];
       }
     }
+    if constexpr (DI && WV == 3) {
+      // tile j - 1 (written before the last barrier; wave 0 fills the other buffer now)
+      if (j > 0) {
+        cpx<double>* Di = reinterpret_cast<cpx<double>*>(smem + dioff);
+        diag_tile_invert(Di + ((j - 1) & 1) * kDiTSZ, Di + 2 * kDiTSZ, Lf, j - 1, K, lane);
+      }
+    }
     __syncthreads();   // the panel L_.j is in P
     if (j + 1 < Tn) {
       if constexpr (WV >= 0) trail_step_w<TM, (WV >= 0 ? WV : 0)>(P, Pn, j, Tn, gr, gi);
       else trail_step<TM>(P, Pn, j, wave, Tn, gr, gi);
     }
   }
+  if constexpr (DI && WV == 3) {
+    cpx<double>* Di = reinterpret_cast<cpx<double>*>(smem + dioff);
+    diag_tile_invert(Di + ((Tn - 1) & 1) * kDiTSZ, Di + 2 * kDiTSZ, Lf, Tn - 1, K, lane);
+  }
 }
 
-template <int TM, int HP, bool EM>
+// blockIdx.y: the block of a grouped launch (one launch over a rank's blocks: Zh, Bh, Wb, L
+// and h advance by their per-block extents; ds is the same for every block).  gridDim.x stays
+// a multiple of 8, so the linear workgroup id mod 8 (the XCD) is blockIdx.x & 7 for every y.
+template <int TM, int HP, bool EM, bool DI>
 __global__ __launch_bounds__(kGcNT, GcShape<TM>::WGS) void k_gram_chol_mf(const cpx<double>* __restrict__ Zh,
                                                            const cpx<double>* __restrict__ Bh,
                                                            cpx<double>* __restrict__ L,
                                                            cpx<double>* __restrict__ h, int F,
                                                            int K, int ni, double rho, int NV,
                                                            const cpx<double>* __restrict__ Wb,
-                                                           const cpx<double>* __restrict__ ds) {
+                                                           const cpx<double>* __restrict__ ds,
+                                                           int dioff) {
   const int per = gridDim.x >> 3;
   const int fz = (blockIdx.x & 7) * per + (blockIdx.x >> 3);   // XCD-aware: neighbours share L2
   if (fz >= F) return;
   const int f = EM ? zl::slot_bin(fz) : fz;   // EM: bin slots in turn, fz the bin in the inputs' order
+  const int64_t blk = blockIdx.y;
+  if (blk) {
+    Zh += blk * ni * K * F;
+    Bh += blk * ni * NV * F;
+    if constexpr (EM) Wb += blk * ni * F;
+    L += blk * F * (K * (K + 1) / 2);
+    h += blk * F * NV * K;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if constexpr (TM == 7 && HP > 1) {
-    gram_chol_body<TM, HP, -1, EM>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds);
+    gram_chol_body<TM, HP, -1, EM, false>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds, dioff);
   } else {
     // every wave runs the same barriers in its own instantiation
     switch (__builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6)) {
-      case 0: gram_chol_body<TM, HP, 0, EM>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds); break;
-      case 1: gram_chol_body<TM, HP, 1, EM>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds); break;
-      case 2: gram_chol_body<TM, HP, 2, EM>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds); break;
-      default: gram_chol_body<TM, HP, 3, EM>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds); break;
+      case 0: gram_chol_body<TM, HP, 0, EM, DI>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds, dioff); break;
+      case 1: gram_chol_body<TM, HP, 1, EM, DI>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds, dioff); break;
+      case 2: gram_chol_body<TM, HP, 2, EM, DI>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds, dioff); break;
+      default: gram_chol_body<TM, HP, 3, EM, DI>(Zh, Bh, L, h, F, K, ni, rho, NV, f, fz, smem, Wb, ds, dioff); break;
     }
   }
 }
@@ -551,6 +591,13 @@ static size_t gc_lds_cap(int K) { return (size_t)(gc_tm(K) <= 7 ? 80 : 160) * 10
 bool gram_chol_mf_emit_ok(int K, int NV, int ni) {
   return gram_chol_mf_ok(K, NV) && ni > 0 && gram_chol_mf_smem(NV, K, ni) <= gc_lds_cap(K);
 }
+// the fused inversion: the TM = 7, one-h-entry-per-thread kernels (per-wave instantiations),
+// and its three tiles beside the staging buffers still leave the CU to two workgroups
+constexpr size_t kGcDiBytes = (size_t)3 * kDiTSZ * 16;
+bool gram_chol_mf_dinv_ok(int K, int NV, int ni) {
+  return gram_chol_mf_ok(K, NV) && gc_tm(K) == 7 && K * NV <= kGcNT &&
+         gram_chol_mf_smem(NV, K, ni) + kGcDiBytes <= gc_lds_cap(K);
+}
 
 // ni > 0: the staging form of the emitted spectra, which also holds the bin's filter values
 // and the block's ni w values (whole chunks)
@@ -562,34 +609,43 @@ size_t gram_chol_mf_smem(int NV, int K, int ni) {
   return stage > chol ? stage : chol;
 }
 
-template <int TM, int HP>
+template <int TM, int HP, bool DI>
 static void gram_chol_mf_go(const cpx<double>* Zh, const cpx<double>* Bh, cpx<double>* L,
                             cpx<double>* h, int F, int K, int ni, double rho, int NV,
-                            hipStream_t st, const cpx<double>* Wb, const cpx<double>* ds) {
-  const int grid = ((F + 7) / 8) * 8;
+                            hipStream_t st, const cpx<double>* Wb, const cpx<double>* ds,
+                            int nblocks) {
+  const dim3 grid(((F + 7) / 8) * 8, nblocks);
+  // the inversion's tiles past max(staging, panels)
+  const size_t base = gram_chol_mf_smem(NV, K, Wb ? ni : 0);
+  const size_t smem = base + (DI ? kGcDiBytes : 0);
   if (Wb)
-    hipLaunchKernelGGL((k_gram_chol_mf<TM, HP, true>), dim3(grid), dim3(kGcNT),
-                       gram_chol_mf_smem(NV, K, ni), st, Zh, Bh, L, h, F, K, ni, rho, NV, Wb, ds);
+    hipLaunchKernelGGL((k_gram_chol_mf<TM, HP, true, DI>), grid, dim3(kGcNT), smem, st, Zh, Bh, L,
+                       h, F, K, ni, rho, NV, Wb, ds, (int)base);
   else
-    hipLaunchKernelGGL((k_gram_chol_mf<TM, HP, false>), dim3(grid), dim3(kGcNT),
-                       gram_chol_mf_smem(NV, K, 0), st, Zh, Bh, L, h, F, K, ni, rho, NV, Wb, ds);
+    hipLaunchKernelGGL((k_gram_chol_mf<TM, HP, false, DI>), grid, dim3(kGcNT), smem, st, Zh, Bh,
+                       L, h, F, K, ni, rho, NV, Wb, ds, (int)base);
 }
 
 hipError_t launch_gram_chol_mf(const cpx<double>* Zh, const cpx<double>* Bh, cpx<double>* L,
                                cpx<double>* h, int F, int K, int ni, double rho, int NV,
-                               hipStream_t st, const cpx<double>* Wb, const cpx<double>* ds) {
-  if (!gram_chol_mf_ok(K, NV)) return hipErrorInvalidValue;
+                               hipStream_t st, const cpx<double>* Wb, const cpx<double>* ds,
+                               int nblocks, bool dinv) {
+  if (nblocks <= 0) return hipSuccess;
+  if (!gram_chol_mf_ok(K, NV) || nblocks > 65535) return hipErrorInvalidValue;
   // the emitted form reads bin slots of the 110 x 110 grid's half spectrum
   if ((Wb != nullptr) != (ds != nullptr)) return hipErrorInvalidValue;
   if (Wb && (F != zl::F || NV != 1 || !gram_chol_mf_emit_ok(K, NV, ni))) return hipErrorInvalidValue;
+  if (dinv && !gram_chol_mf_dinv_ok(K, NV, Wb ? ni : 0)) return hipErrorInvalidValue;
   switch (gc_tm(K)) {
     case 7:
-      if (K * NV <= kGcNT) gram_chol_mf_go<7, 1>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds);
-      else gram_chol_mf_go<7, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds);
+      if (K * NV <= kGcNT) {
+        if (dinv) gram_chol_mf_go<7, 1, true>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds, nblocks);
+        else gram_chol_mf_go<7, 1, false>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds, nblocks);
+      } else gram_chol_mf_go<7, kGcHPT, false>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds, nblocks);
       break;
-    case 8: gram_chol_mf_go<8, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds); break;
-    case 10: gram_chol_mf_go<10, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds); break;
-    default: gram_chol_mf_go<12, kGcHPT>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds); break;
+    case 8: gram_chol_mf_go<8, kGcHPT, false>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds, nblocks); break;
+    case 10: gram_chol_mf_go<10, kGcHPT, false>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds, nblocks); break;
+    default: gram_chol_mf_go<12, kGcHPT, false>(Zh, Bh, L, h, F, K, ni, rho, NV, st, Wb, ds, nblocks); break;
   }
   return hipGetLastError();
 }

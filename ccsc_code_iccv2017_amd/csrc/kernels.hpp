@@ -116,10 +116,15 @@ hipError_t launch_gram_chol(const cpx<T>* Zh, const cpx<T>* Bh, cpx<T>* L, cpx<T
 // L and h stay in natural bin order.
 bool gram_chol_mf_ok(int K, int NV);
 bool gram_chol_mf_emit_ok(int K, int NV, int ni);   // the Wb / ds form (the block's w fits the LDS)
+// nblocks > 1: one launch over nblocks consecutive blocks (Zh, Bh, Wb, L and h contiguous over
+// the blocks, ds shared).  dinv (gram_chol_mf_dinv_ok; ni = 0 without Wb): the kernel leaves
+// L_jj^-1 in the diagonal tiles' slots itself, what launch_invert_diag would make of its L.
+bool gram_chol_mf_dinv_ok(int K, int NV, int ni);
 hipError_t launch_gram_chol_mf(const cpx<double>* Zh, const cpx<double>* Bh, cpx<double>* L,
                                cpx<double>* h, int F, int K, int ni, double rho, int NV,
                                hipStream_t st, const cpx<double>* Wb = nullptr,
-                               const cpx<double>* ds = nullptr);
+                               const cpx<double>* ds = nullptr, int nblocks = 1,
+                               bool dinv = false);
 // The same outputs for 192 < K <= 400 (gramchol_big.hip): the block's code spectra
 // transposed into X ([F][ni][K], ni K F complex of workspace), the Gram on the matrix
 // cores into the packed slots of L, then a left-looking Cholesky in place.
@@ -156,6 +161,48 @@ hipError_t launch_dsolve(const cpx<T>* L, const cpx<T>* h, const cpx<T>* Ch, cpx
 // read once per solve instead of twice.
 bool dsolve_tile_ok(int K, int NV);
 hipError_t launch_invert_diag(cpx<double>* L, int F, int K, hipStream_t st);
+// The inversion of one diagonal tile by one wave, shared by k_invert_diag (dstep.hip, the
+// tile read back from the packed factor) and k_gram_chol_mf's fused form (gramchol.hip, the
+// tile from the panel sweep's registers): the same staging rule, substitution and scaling,
+// so both leave the same bits.  An LDS tile holds element (row, col) at col * kDiTS + row.
+constexpr int kDiTS = 17;
+constexpr int kDiTSZ = 16 * kDiTS;
+__device__ __forceinline__ void wave_sync_lds() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+// staged element (r, cc) of diagonal tile J: the factor's entry on and below the diagonal
+// of a real row (ld() fetches it), identity above it and on the padding rows R >= K
+template <typename Ld>
+__device__ __forceinline__ cpx<double> diag_tile_elem(int J, int r, int cc, int K, Ld&& ld) {
+  return (r >= cc && 16 * J + r < K) ? ld() : cpx<double>{(r == cc) ? 1.0 : 0.0, 0.0};
+}
+// Lw staged (and visible to the wave): lane c & 15 forms column c of M = L_JJ^-1 by forward
+// substitution into the wave's LDS copy Mw (each lane reads back only its own column; the
+// four lanes of a column write the same values):
+//   M[r][c] = (delta_rc - sum_{k<r} L[r][k] M[k][c]) / L[r][r],
+// a row's 2r broadcast reads issued together; then M to the packed slots of tile J
+__device__ __forceinline__ void diag_tile_invert(const cpx<double>* Lw, cpx<double>* Mw,
+                                                 cpx<double>* Lf, int J, int K, int lane) {
+  const int c = lane & 15;
+  for (int r = 0; r < 16; ++r) {
+    cpx<double> s0 = {(r == c) ? 1.0 : 0.0, 0.0}, s1 = {0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 15; ++k) {
+      if (k < r) {
+        const cpx<double> p = cmul(Lw[k * kDiTS + r], Mw[k * kDiTS + c]);
+        if (k & 1) s1 = csub(s1, p);
+        else s0 = csub(s0, p);
+      }
+    }
+    Mw[r * kDiTS + c] = cscale(cadd(s0, s1), 1.0 / Lw[r * kDiTS + r].x);
+  }
+  if (lane < 16) {
+    const int C = 16 * J + c;
+    for (int r = c; r < 16 && 16 * J + r < K; ++r)
+      Lf[C * K - (C * (C - 1)) / 2 + 16 * J + r - C] = Mw[r * kDiTS + c];
+  }
+}
 hipError_t launch_dsolve_tile(const cpx<double>* L, const cpx<double>* h, const cpx<double>* Ch,
                               cpx<double>* Dh, int nblocks, int F, int K, double rho, int NV,
                               hipStream_t st);

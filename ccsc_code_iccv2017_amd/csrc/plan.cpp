@@ -495,6 +495,13 @@ Route route2d(const ccsc_problem& p, const Geom& g, int rank, int nranks, bool r
     rt.zemit = rt.z == ZStep::Line && !(p.tol > 0) && rt.dfactor == DFactor::Mfma && !rt.h_sep &&
                !objective_refresh(p) && !p.trace_objective && gram_chol_mf_emit_ok(K, NV, ni) &&
                env_on("CCSC_ZEMIT");
+    const bool dg = env_on("CCSC_DGROUP");
+    // (blockIdx.y carries the block: a rank of more blocks keeps the per-block loop)
+    rt.dgroup = rt.zemit && dg && rt.nb <= 65535;
+    // (the emitted form's staging is the larger of the kernel's two)
+    rt.dinv = dg && rt.dsolve == DSolve::Tile && rt.dfactor == DFactor::Mfma && !rt.h_sep &&
+              gram_chol_mf_dinv_ok(K, NV, rt.zemit ? ni : 0);
+    if (rt.dinv) rt.st2 = false;
   }
   if (rt.z == ZStep::Planes3) {
     // fused t-FFT + z-solve (k_tsolve3): TC x' columns per workgroup; C4 (74x74x42,

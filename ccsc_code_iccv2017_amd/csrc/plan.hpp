@@ -124,6 +124,14 @@ struct Route {
   // route) and the next D-precompute's Gram reads them instead of a k_zhat_line pass;
   // CCSC_ZEMIT=0 keeps that pass
   bool zemit = false;
+  // zemit: every local block's spectra lie in `yz` before the precompute starts, so it runs
+  // as one k_gram_chol_mf launch over the rank's blocks (steps that start from a materialised
+  // state keep the per-block loop); CCSC_DGROUP=0 keeps one launch per block, and dinv off
+  bool dgroup = false;
+  // tile d-solve on the MFMA factor: k_gram_chol_mf leaves the inverted diagonal tiles
+  // itself (no k_invert_diag, no side stream) where its TM = 7 per-wave form serves the
+  // problem (K NV <= 256) and the three extra LDS tiles still leave a CU to two workgroups
+  bool dinv = false;
 };
 // consensus learners (dP, dZ, 3D, 4D) / the 2-3D learner; the problem resolved, g from
 // check_supported.  route_hs throws for several ranks past K = 192.

@@ -245,7 +245,10 @@ int32_t ccsc_session_results(ccsc_session* s, ccsc_outputs* out, char* err, size
 int32_t ccsc_session_iterlog(ccsc_session* s, ccsc_iterlog* log, char* err, size_t errlen);
 /* Per-kernel timing with HIP events on the engine stream.  kernel ids: 0 = fused
  * z-step, 1 = gram+cholesky, 2 = d-solve, 3 = dual+R2C, 4 = C2R+support.  Returns
- * launches, total milliseconds and the algorithmic bytes of ONE launch. */
+ * launches, total milliseconds and the algorithmic bytes of ONE launch.  Kernel 1 launches
+ * once per block or, where the precompute is grouped, once per outer iteration over the
+ * rank's blocks: its bytes are those of one block times the mean number of blocks per launch
+ * timed so far, so launches x bytes is what the timed launches moved. */
 int32_t ccsc_session_set_profiling(ccsc_session* s, int32_t on);
 int32_t ccsc_session_kernel_stats(ccsc_session* s, int32_t kernel_id, int64_t* launches,
                                   double* total_ms, double* alg_bytes_per_launch, char* err,
