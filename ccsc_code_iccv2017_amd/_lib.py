@@ -58,6 +58,7 @@ class Problem(C.Structure):
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_lp = C.POINTER(C.c_int64)
 
 
 class Outputs(C.Structure):
@@ -212,6 +213,22 @@ SIGNATURES = {
     "ccsc_unstandardize_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int64, C.c_int64, C.c_char_p,
                                            C.c_size_t]),
+    "ccsc_session_codes_count": (C.c_int32, [C.c_void_p, C.c_double, _lp, _lp, _lp, C.c_char_p,
+                                             C.c_size_t]),
+    "ccsc_session_codes_fill": (C.c_int32, [C.c_void_p, C.c_double, _lp, _dp, C.c_int64,
+                                            C.c_char_p, C.c_size_t]),
+    "ccsc_sparsify_count": (C.c_int32, [C.c_void_p, _dp, C.c_int64, C.c_int64, C.c_double, _lp,
+                                        C.c_char_p, C.c_size_t]),
+    "ccsc_sparsify_fill": (C.c_int32, [C.c_void_p, _dp, C.c_int64, C.c_int64, C.c_double, _lp,
+                                       _dp, C.c_int64, C.c_char_p, C.c_size_t]),
+    "ccsc_sparsify_count_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                            C.c_double, C.c_void_p, C.c_char_p, C.c_size_t]),
+    "ccsc_sparsify_fill_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                           C.c_double, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_char_p, C.c_size_t]),
+    "ccsc_test_codes_index": (C.c_int32, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int64, C.c_int64, C.c_int32, _lp, C.c_char_p,
+                                          C.c_size_t]),
     "ccsc_test_fft2d": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
                                     C.c_char_p, C.c_size_t]),
     "ccsc_test_fft_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -275,3 +292,9 @@ def iptr(a):
     if a is None:
         return C.cast(None, _ip)
     return a.ctypes.data_as(_ip)
+
+
+def lptr(a):
+    if a is None:
+        return C.cast(None, _lp)
+    return a.ctypes.data_as(_lp)

@@ -1153,6 +1153,16 @@ struct Session2D {
     if (out->obj_val) *out->obj_val = objective(dhat.as<cpx<double>>(), nullptr);
   }
 
+  // The codes as results() would copy them into z_res: the natural-order `z`, one column
+  // of M = X Y (T) K values per local patch.  Leaves the session as that copy leaves it.
+  const double* codes_dense(int64_t* M, int64_t* n) {
+    materialize_z();
+    HIPCHK(hipStreamSynchronize(st));
+    *n = np;
+    *M = (int64_t)(z.bytes / sizeof(double)) / np;
+    return z.as<double>();
+  }
+
   double alg_bytes(int id) const {
     const double Pd = P, Fd = F, Kd = K;
     switch (id) {
@@ -1589,6 +1599,14 @@ struct SessionHS {
     }
     if (out->obj_val) *out->obj_val = obj;   // the last objective the learner evaluated
   }
+
+  // The codes as results() copies them into z_res: one column of X Y K values per image.
+  const double* codes_dense(int64_t* M, int64_t* nloc) {
+    HIPCHK(hipStreamSynchronize(st));
+    *nloc = n;
+    *M = (int64_t)K * P;
+    return z.as<double>();
+  }
 };
 
 }  // namespace ccsc
@@ -2007,6 +2025,39 @@ int32_t ccsc_session_results(ccsc_session* s, ccsc_outputs* out, char* err, size
     HIPCHK(hipSetDevice(s->ctx()->device));
     if (s->hs) s->hs->results(out);
     else s->s2->results(out);
+  });
+}
+
+int32_t ccsc_session_codes_count(ccsc_session* s, double eps, int64_t* jc, int64_t* rows,
+                                 int64_t* cols, char* err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    codes_check_eps(eps);
+    if (!jc) throw Err(CCSC_E_INVALID, "NULL jc");
+    need_session(s);
+    HIPCHK(hipSetDevice(s->ctx()->device));
+    int64_t M = 0, n = 0;
+    const double* z = s->hs ? s->hs->codes_dense(&M, &n) : s->s2->codes_dense(&M, &n);
+    codes_check_shape(M, n);
+    jc[0] = 0;
+    codes_count_dev(s->ctx(), z, M, n, eps, jc);
+    if (rows) *rows = M;
+    if (cols) *cols = n;
+  });
+}
+
+int32_t ccsc_session_codes_fill(ccsc_session* s, double eps, int64_t* ir, double* pr,
+                                int64_t capacity, char* err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    codes_check_fill_args(eps, ir, pr, capacity);
+    need_session(s);
+    HIPCHK(hipSetDevice(s->ctx()->device));
+    int64_t M = 0, n = 0;
+    const double* z = s->hs ? s->hs->codes_dense(&M, &n) : s->s2->codes_dense(&M, &n);
+    codes_check_shape(M, n);
+    std::vector<int64_t> jc((size_t)n + 1, 0);
+    codes_count_dev(s->ctx(), z, M, n, eps, jc.data());
+    codes_check_capacity(capacity, jc[(size_t)n]);
+    codes_fill_dev(s->ctx(), z, M, n, eps, jc.data(), ir, pr, false);
   });
 }
 

@@ -220,3 +220,19 @@ struct ccsc_ctx {
   // enqueue + wait_comm, abort / re-init) executes on a one-GPU box
   bool rccl_self = false;
 };
+
+namespace ccsc {
+// codes.cpp: the dense -> compressed-sparse-column path over a device matrix a, column-major
+// [M, n], on ctx's stream; both return with the stream idle.
+void codes_check_eps(double eps);                  // CCSC_E_INVALID unless eps >= 0
+void codes_check_shape(int64_t M, int64_t n);      // CCSC_E_UNSUPPORTED from 2^31 rows
+void codes_check_fill_args(double eps, const int64_t* ir, const double* pr, int64_t capacity);
+void codes_check_capacity(int64_t capacity, int64_t nnz);
+// jc[0] is the offset of the first column on entry; fills jc[1 .. n] (host)
+void codes_count_dev(ccsc_ctx* ctx, const double* a, int64_t M, int64_t n, double eps,
+                     int64_t* jc);
+// column c's kept entries go to ir / pr [jc[c], jc[c + 1]) (host arrays, or device arrays
+// with out_dev); jc as codes_count_dev left it for the same matrix
+void codes_fill_dev(ccsc_ctx* ctx, const double* a, int64_t M, int64_t n, double eps,
+                    const int64_t* jc, int64_t* ir, double* pr, bool out_dev);
+}  // namespace ccsc

@@ -21,6 +21,12 @@ column-major, so a Fortran-ordered NumPy array is bit-for-bit an mxArray.
 'z': size_z}`` (dZ: ``size_z_crop`` = [X, Y, K, ni], replicated per block).
 With ``init=None`` the engine draws d0/z0 on the device from ``seed``.
 
+The five learners take ``sparse_z=eps``: the z_res position of the return then holds the
+compressed sparse column tuple ``(jc, ir, pr, (M, n))`` of ``Session.codes_sparse(eps)``
+-- the entries with ``not (abs(z) <= eps)``, thresholded on the GPU -- and the dense z
+(97 GB at 10^4 patches) is never allocated.  This runs through a ``Session``, so a
+device-list context raises ``CCSCError`` (sessions run on a one-device context).
+
 Errors are raised as ``CCSCError`` (the MATLAB reference raises on bad shapes
 too; ``n % ni != 0`` is an error here rather than a silent floor, Q13).
 """
@@ -298,6 +304,33 @@ class Session:
         L.check(L.lib().ccsc_session_results(self.ptr, C.byref(out), eb, len(eb)), eb)
         return d_res, z_res, DZ, (float(obj[0]) if want_obj else None)
 
+    def codes_sparse(self, eps, as_scipy=False):
+        """The codes as a compressed sparse column matrix, thresholded on the GPU: one column
+        per local patch (2-3D: image) with M = X Y (T) K rows, the row index being the
+        column-major index into that patch's slice of ``results()``'s z_res; an entry is kept
+        iff ``not (abs(z) <= eps)`` (a NaN is kept).  Returns ``(jc, ir, pr, (M, n_local))``,
+        int64 / int64 / float64, 0-based, or with ``as_scipy`` a scipy.sparse.csc_matrix
+        (SciPy is imported here, not by the package).  The dense array is never formed on
+        the host; the session is left as ``results(want_z=True)`` leaves it."""
+        eps = float(eps)
+        lib = L.lib()
+        eb = L.errbuf()
+        jc = np.zeros(self.n_local + 1, dtype=np.int64)
+        M, n = C.c_int64(0), C.c_int64(0)
+        L.check(lib.ccsc_session_codes_count(self.ptr, eps, L.lptr(jc), C.byref(M), C.byref(n),
+                                             eb, len(eb)), eb)
+        nnz = int(jc[-1])
+        ir = np.empty(nnz, dtype=np.int64)
+        pr = np.empty(nnz, dtype=np.float64)
+        eb = L.errbuf()
+        L.check(lib.ccsc_session_codes_fill(self.ptr, eps, L.lptr(ir), L.dptr(pr), nnz, eb,
+                                            len(eb)), eb)
+        shape = (M.value, n.value)
+        if as_scipy:
+            from scipy.sparse import csc_matrix
+            return csc_matrix((pr, ir, jc), shape=shape)
+        return jc, ir, pr, shape
+
     def iterlog(self, capacity=None):
         p = self.p
         cap = capacity or (self.outer + 1)
@@ -343,8 +376,67 @@ class Session:
             pass
 
 
+def sparsify(a, eps, ctx=None):
+    """Threshold-and-compact a dense matrix on the GPU (csrc/codes.hip): the entries with
+    ``not (abs(a) <= eps)`` of the 2-D float64 ``a`` as the compressed sparse column triple
+    ``(jc, ir, pr, a.shape)`` -- int64 / int64 / float64, 0-based, rows ascending inside a
+    column, values bit for bit (what scipy.sparse.csc_matrix((pr, ir, jc), shape) takes).  A
+    NumPy array goes through ccsc_sparsify_count / _fill and NumPy arrays come back; a CUDA
+    tensor goes through the _dev forms and everything stays on its device.  ``ctx``: a
+    one-device Context (default: a temporary one on the tensor's / the current device)."""
+    eps = float(eps)
+    lib = L.lib()
+    if a.ndim != 2:
+        raise ValueError("sparsify takes a 2-D matrix [M, n]")
+    M, n = int(a.shape[0]), int(a.shape[1])
+    if hasattr(a, "is_cuda"):
+        import torch
+        if not a.is_cuda:
+            raise ValueError("sparsify takes a NumPy array or a CUDA tensor")
+        x = a.to(torch.float64).t().contiguous()        # [n, M] row-major = [M, n] column-major
+        dev = a.device.index if a.device.index is not None else torch.cuda.current_device()
+        jc = torch.empty(n + 1, dtype=torch.int64, device=a.device)
+        own = ctx is None
+        if own:
+            ctx = Context(dev)
+        try:
+            torch.cuda.synchronize(a.device)
+            eb = L.errbuf()
+            L.check(lib.ccsc_sparsify_count_dev(ctx.ptr, x.data_ptr(), M, n, eps, jc.data_ptr(),
+                                                eb, len(eb)), eb)
+            nnz = int(jc[-1].item())
+            ir = torch.empty(nnz, dtype=torch.int64, device=a.device)
+            pr = torch.empty(nnz, dtype=torch.float64, device=a.device)
+            eb = L.errbuf()
+            L.check(lib.ccsc_sparsify_fill_dev(ctx.ptr, x.data_ptr(), M, n, eps, ir.data_ptr(),
+                                               pr.data_ptr(), nnz, eb, len(eb)), eb)
+        finally:
+            if own:
+                ctx.close()
+        return jc, ir, pr, (M, n)
+    x = np.asfortranarray(a, dtype=np.float64)
+    jc = np.zeros(n + 1, dtype=np.int64)
+    own = ctx is None
+    if own:
+        import torch
+        ctx = Context(torch.cuda.current_device())
+    try:
+        eb = L.errbuf()
+        L.check(lib.ccsc_sparsify_count(ctx.ptr, L.dptr(x), M, n, eps, L.lptr(jc), eb, len(eb)), eb)
+        nnz = int(jc[-1])
+        ir = np.empty(nnz, dtype=np.int64)
+        pr = np.empty(nnz, dtype=np.float64)
+        eb = L.errbuf()
+        L.check(lib.ccsc_sparsify_fill(ctx.ptr, L.dptr(x), M, n, eps, L.lptr(ir), L.dptr(pr), nnz,
+                                       eb, len(eb)), eb)
+    finally:
+        if own:
+            ctx.close()
+    return jc, ir, pr, (M, n)
+
+
 def _learn_2d(variant, b, kernel_size, lambda_residual, lambda_prior, max_it, tol, verbose, init,
-              ctx=None, device=0, want_z=True, want_DZ=True, **kw):
+              ctx=None, device=0, want_z=True, want_DZ=True, sparse_z=None, **kw):
     b = np.asarray(b, dtype=np.float64)
     if b.ndim == 2:
         b = b[:, :, None]
@@ -360,14 +452,16 @@ def _learn_2d(variant, b, kernel_size, lambda_residual, lambda_prior, max_it, to
         if init is not None and len(init) > 0:
             d0 = init.get("d")
             z0 = init.get("z")
-        if ctx.group:
+        if ctx.group and sparse_z is None:
             return learn_once(ctx, p, b, d0, z0, want_z=want_z, want_DZ=want_DZ)
-        s = Session(ctx, p, b, d0, z0)
+        s = Session(ctx, p, b, d0, z0)   # sparse_z on a device list: "one-device context"
         try:
             done = False
             while s.outer < s.p.max_it and not done:
                 done = s.step(1)
-            d_res, z_res, DZ, _ = s.results(want_z=want_z, want_DZ=want_DZ)
+            d_res, z_res, DZ, _ = s.results(want_z=want_z and sparse_z is None, want_DZ=want_DZ)
+            if sparse_z is not None:
+                z_res = s.codes_sparse(sparse_z)
             iterations = s.iterlog()
         finally:
             s.close()
@@ -441,10 +535,10 @@ def admm_learn_conv2D_large_dzParallel(b, kernel_size, lambda_residual, lambda_p
                      verbose, init, **kw)
 
 
-def _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ):
+def _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ, sparse_z=None):
     """The 3D / 4D learners' run: a session stepped to the end on one device, one
     ccsc_learn over the whole problem on a multi-device context (as _learn_2d)."""
-    if ctx.group:
+    if ctx.group and sparse_z is None:
         d_res, z_res, DZ, log = learn_once(ctx, p, b, d0, z0, want_z=want_z, want_DZ=want_DZ,
                                            want_obj=True)
         return d_res, z_res, DZ, log["obj_val"], log
@@ -453,7 +547,10 @@ def _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ):
         done = False
         while s.outer < s.p.max_it and not done:
             done = s.step(1)
-        d_res, z_res, DZ, obj = s.results(want_z=want_z, want_DZ=want_DZ, want_obj=True)
+        d_res, z_res, DZ, obj = s.results(want_z=want_z and sparse_z is None, want_DZ=want_DZ,
+                                          want_obj=True)
+        if sparse_z is not None:
+            z_res = s.codes_sparse(sparse_z)
         log = s.iterlog()
     finally:
         s.close()
@@ -462,7 +559,7 @@ def _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ):
 
 def admm_learn_conv4D_lightfield(b, kernel_size, lambda_residual, lambda_prior, max_it, tol,
                                  verbose, init=None, ctx=None, device=0, want_z=True,
-                                 want_DZ=True, **kw):
+                                 want_DZ=True, sparse_z=None, **kw):
     """Drop-in for 4D/admm_learn_conv4D_lightfield.m:1-212.
 
     b: [x, y, U, V, n] (single in the reference driver, Q15: widened to double);
@@ -488,19 +585,20 @@ def admm_learn_conv4D_lightfield(b, kernel_size, lambda_residual, lambda_prior, 
             z0 = init.get("z")
             if z0 is not None:
                 z0 = np.real(np.asarray(z0))
-        d_res, z_res, DZ, obj, log = _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ)
+        d_res, z_res, DZ, obj, log = _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ, sparse_z)
     finally:
         if own:
             ctx.close()
     iterations = {"obj_vals_d": [], "obj_vals_z": [], "tim_vals": [], "it_vals": [],
                   "trace": log["trace"], "engine_tim_vals": log["tim_vals"]}
-    if z_res is not None:
+    if z_res is not None and sparse_z is None:
         z_res = z_res.astype(np.complex128)
     return d_res, z_res, DZ, obj, iterations
 
 
 def admm_learn_conv3D_large(b, kernel_size, lambda_residual, lambda_prior, max_it, tol, verbose,
-                            init=None, ctx=None, device=0, want_z=True, want_DZ=True, **kw):
+                            init=None, ctx=None, device=0, want_z=True, want_DZ=True,
+                            sparse_z=None, **kw):
     """Drop-in for 3D/admm_learn_conv3D_large.m:1-230 (function admm_learn_convND_large).
 
     b: [x, y, t, n]; kernel_size = [psf, psf, psf, K].  Returns (d_res [psf,psf,psf,K],
@@ -522,7 +620,7 @@ def admm_learn_conv3D_large(b, kernel_size, lambda_residual, lambda_prior, max_i
         if init is not None and len(init) > 0:
             d0 = init.get("d")
             z0 = init.get("z")
-        d_res, z_res, DZ, obj, log = _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ)
+        d_res, z_res, DZ, obj, log = _learn_nd(ctx, p, b, d0, z0, want_z, want_DZ, sparse_z)
     finally:
         if own:
             ctx.close()
@@ -533,7 +631,7 @@ def admm_learn_conv3D_large(b, kernel_size, lambda_residual, lambda_prior, max_i
 
 def admm_learn(b, kernel_size, lambda_residual, lambda_prior, max_it, tol, verbose, init=None,
                smooth_init=None, ctx=None, device=0, want_z=True, want_DZ=True, return_log=False,
-               **kw):
+               sparse_z=None, **kw):
     """Drop-in for 2-3D/DictionaryLearning/admm_learn.m:1-237 (hyperspectral learner).
 
     b, smooth_init: [x, y, W, n] (learn_hyperspectral.m:16-17 passes the 13x13 Gaussian
@@ -568,7 +666,10 @@ def admm_learn(b, kernel_size, lambda_residual, lambda_prior, max_it, tol, verbo
             done = False
             while s.outer < s.p.max_it and not done:
                 done = s.step(1)
-            d_res, z_res, DZ, obj = s.results(want_z=want_z, want_DZ=want_DZ, want_obj=True)
+            d_res, z_res, DZ, obj = s.results(want_z=want_z and sparse_z is None,
+                                              want_DZ=want_DZ, want_obj=True)
+            if sparse_z is not None:
+                z_res = s.codes_sparse(sparse_z)
             log = s.iterlog()
         finally:
             s.close()

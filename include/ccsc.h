@@ -243,6 +243,25 @@ int32_t ccsc_session_step(ccsc_session* s, int32_t n_outer, int32_t* done, char*
 int32_t ccsc_session_objective(ccsc_session* s, double* obj, char* err, size_t errlen);
 int32_t ccsc_session_results(ccsc_session* s, ccsc_outputs* out, char* err, size_t errlen);
 int32_t ccsc_session_iterlog(ccsc_session* s, ccsc_iterlog* log, char* err, size_t errlen);
+/* The codes as a compressed sparse column matrix (MATLAB's sparse, scipy.sparse.csc_matrix)
+ * instead of the dense z_res: one column per local patch (2-3D: per local image), n_local
+ * columns of M = X Y (T) K rows, the row index being the 0-based column-major index into
+ * that patch's [X, Y, (T), K] slice of z_res (4D: of the real [X, Y, 1, 1, K] slice).  An entry
+ * is kept iff !(|z| <= eps): strictly above the threshold, and a NaN is kept.  eps >= 0
+ * (+inf keeps only NaNs, 0 keeps every nonzero); a negative or NaN eps is CCSC_E_INVALID,
+ * M >= 2^31 CCSC_E_UNSUPPORTED.  Two steps: the count call fills jc[0 .. n_local] (the
+ * caller learns nnz = jc[n_local]; rows / cols, nullable, receive M and n_local), the fill
+ * call takes caller-allocated ir[capacity], pr[capacity]: row indices strictly ascending
+ * inside a column, pr the dense values' bits unchanged, everything 0-based.  A capacity below
+ * nnz is CCSC_E_INVALID with the needed count in the message and nothing written.  Both
+ * materialise the codes as the results call with z_res set does and leave the session in
+ * the state that call leaves it in; the dense array never exists on the host (the triple is
+ * formed on the device chunk by chunk, see the sparsify entry points below).  The result is
+ * bitwise reproducible and does not depend on the chunking or on the other patches. */
+int32_t ccsc_session_codes_count(ccsc_session* s, double eps, int64_t* jc, int64_t* rows,
+                                 int64_t* cols, char* err, size_t errlen);
+int32_t ccsc_session_codes_fill(ccsc_session* s, double eps, int64_t* ir, double* pr,
+                                int64_t capacity, char* err, size_t errlen);
 /* Per-kernel timing with HIP events on the engine stream.  kernel ids: 0 = fused
  * z-step, 1 = gram+cholesky, 2 = d-solve, 3 = dual+R2C, 4 = C2R+support.  Returns
  * launches, total milliseconds and the algorithmic bytes of ONE launch.  Kernel 1 launches
@@ -451,6 +470,39 @@ int32_t ccsc_unstandardize(ccsc_ctx* ctx, const double* in, double* out, const d
 int32_t ccsc_unstandardize_dev(ccsc_ctx* ctx, const double* in, double* out, const double* mean,
                                const double* sdev, int64_t planes, int64_t N, char* err,
                                size_t errlen);
+
+/* Threshold-and-compact of any dense matrix into compressed sparse columns: a is column-major
+ * [M, n] float64; entry (i, j) is kept iff !(|a| <= eps) (see the session form above for
+ * eps, the layout and the two-step protocol: jc[n + 1], then ir / pr [capacity], int64 / int64 /
+ * double, 0-based, rows ascending inside a column, values bit for bit).  The host forms take
+ * host arrays and stage the matrix in chunks of columns; the _dev forms take a, jc, ir and pr
+ * on the context's device (e.g. torch tensors).  All run on the context's stream,
+ * synchronise on return and take a one-device context only.  They validate eps, the outputs
+ * and the shape before they touch the device; M == 0 or n == 0 gives an empty matrix.
+ * Per tile of 2048 rows of a column a count pass finds the kept entries with wave ballots,
+ * a 64-bit exclusive scan over the tiles places them, and a scatter gives each lane its slot
+ * from the ballot's lower lanes: index order with no sort and no atomics, so the result
+ * is bitwise reproducible, the same for every chunking and for a column taken alone.  The
+ * workspace (8 B per tile, and for host outputs 16 B per kept entry) is allocated inside the
+ * call and freed before return; columns go in chunks that keep it within 256 MiB whatever
+ * n is (a single column that needs more gets its own).  Environment, read per call:
+ * CCSC_CODES_WS_MB=<MiB> lowers that budget (0: one column per chunk). */
+int32_t ccsc_sparsify_count(ccsc_ctx* ctx, const double* a, int64_t M, int64_t n, double eps,
+                            int64_t* jc, char* err, size_t errlen);
+int32_t ccsc_sparsify_fill(ccsc_ctx* ctx, const double* a, int64_t M, int64_t n, double eps,
+                           int64_t* ir, double* pr, int64_t capacity, char* err, size_t errlen);
+int32_t ccsc_sparsify_count_dev(ccsc_ctx* ctx, const double* a, int64_t M, int64_t n, double eps,
+                                int64_t* jc, char* err, size_t errlen);
+int32_t ccsc_sparsify_fill_dev(ccsc_ctx* ctx, const double* a, int64_t M, int64_t n, double eps,
+                               int64_t* ir, double* pr, int64_t capacity, char* err,
+                               size_t errlen);
+/* Host only: the index arithmetic of the kernels above, for checks with offsets past 2^32
+ * that no test-sized matrix reaches.  For lane `lane` of step `step` of wave `wave` in tile
+ * `tile` of a chunk of columns of M rows: out4 = {column, row, element index column * M + row,
+ * slot tile_off + before + prefix}.  wave 0..3, step 0..7, lane and prefix 0..63. */
+int32_t ccsc_test_codes_index(int64_t M, int64_t tile, int32_t wave, int32_t step, int32_t lane,
+                              int64_t tile_off, int64_t before, int32_t prefix, int64_t* out4,
+                              char* err, size_t errlen);
 
 /* ---- kernel-level entry points (parity tests of single stages) ---------- */
 /* 2D R2C of `count` real slices [X,Y] -> half spectra [Y][X/2+1] (re,im). */
