@@ -229,6 +229,18 @@ SIGNATURES = {
     "ccsc_test_codes_index": (C.c_int32, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int64, C.c_int64, C.c_int32, _lp, C.c_char_p,
                                           C.c_size_t]),
+    "ccsc_synthesize": (C.c_int32, [C.c_void_p, _dp, _ip, C.c_int32, C.c_int32, _ip, _lp, _lp, _dp,
+                                    C.c_int64, C.c_int64, _dp, C.c_char_p, C.c_size_t]),
+    "ccsc_synthesize_dev": (C.c_int32, [C.c_void_p, C.c_void_p, _ip, C.c_int32, C.c_int32, _ip,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                        C.c_void_p, C.c_char_p, C.c_size_t]),
+    "ccsc_densify": (C.c_int32, [C.c_void_p, _lp, _lp, _dp, C.c_int64, C.c_int64, C.c_int64, _dp,
+                                 C.c_char_p, C.c_size_t]),
+    "ccsc_densify_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_int64, C.c_int64, C.c_void_p, C.c_char_p, C.c_size_t]),
+    "ccsc_test_synth_index": (C.c_int32, [_ip, _ip, C.c_int32, C.c_int32, C.c_int64, _ip, _ip,
+                                          _ip, C.c_int32, C.c_int64, _lp, C.c_char_p,
+                                          C.c_size_t]),
     "ccsc_test_fft2d": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
                                     C.c_char_p, C.c_size_t]),
     "ccsc_test_fft_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32,

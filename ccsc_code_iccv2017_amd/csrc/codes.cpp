@@ -17,7 +17,7 @@
 
 namespace ccsc {
 
-static int64_t codes_budget() {
+int64_t codes_budget() {
   int64_t budget = (int64_t)256 << 20;
   if (const char* e = std::getenv("CCSC_CODES_WS_MB")) {
     const long long mb = std::atoll(e);

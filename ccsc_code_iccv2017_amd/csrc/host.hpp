@@ -224,6 +224,7 @@ struct ccsc_ctx {
 namespace ccsc {
 // codes.cpp: the dense -> compressed-sparse-column path over a device matrix a, column-major
 // [M, n], on ctx's stream; both return with the stream idle.
+int64_t codes_budget();   // bytes of workspace per chunk of columns: 256 MiB or CCSC_CODES_WS_MB
 void codes_check_eps(double eps);                  // CCSC_E_INVALID unless eps >= 0
 void codes_check_shape(int64_t M, int64_t n);      // CCSC_E_UNSUPPORTED from 2^31 rows
 void codes_check_fill_args(double eps, const int64_t* ir, const double* pr, int64_t capacity);

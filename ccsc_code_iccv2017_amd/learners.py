@@ -26,6 +26,8 @@ compressed sparse column tuple ``(jc, ir, pr, (M, n))`` of ``Session.codes_spars
 -- the entries with ``not (abs(z) <= eps)``, thresholded on the GPU -- and the dense z
 (97 GB at 10^4 patches) is never allocated.  This runs through a ``Session``, so a
 device-list context raises ``CCSCError`` (sessions run on a one-device context).
+``synthesize(d_res, codes, grid)`` reconstructs ``sum_k d_k (*) z_k`` from such a tuple on
+the GPU and ``densify(codes)`` expands it; ``sparsify`` makes one from any dense matrix.
 
 Errors are raised as ``CCSCError`` (the MATLAB reference raises on bad shapes
 too; ``n % ni != 0`` is an error here rather than a silent floor, Q13).
@@ -433,6 +435,144 @@ def sparsify(a, eps, ctx=None):
         if own:
             ctx.close()
     return jc, ir, pr, (M, n)
+
+
+def _codes_triple(codes):
+    """``(jc, ir, pr, (M, n), on_device)`` of the 4-tuple of ``codes_sparse`` / ``sparsify``
+    or of a scipy.sparse matrix (SciPy is imported only for the latter)."""
+    if isinstance(codes, (tuple, list)):
+        if len(codes) != 4:
+            raise ValueError("codes is the tuple (jc, ir, pr, (M, n)) or a scipy.sparse matrix")
+        jc, ir, pr, shape = codes
+    else:
+        from scipy.sparse import csc_matrix
+        m = csc_matrix(codes)
+        jc, ir, pr, shape = m.indptr, m.indices, m.data, m.shape
+    M, n = int(shape[0]), int(shape[1])
+    dev = [hasattr(a, "is_cuda") for a in (jc, ir, pr)]
+    if any(dev):
+        import torch
+        if not all(dev) or not all(a.is_cuda for a in (jc, ir, pr)):
+            raise ValueError("jc, ir and pr are all NumPy arrays or all CUDA tensors")
+        jc, ir = jc.to(torch.int64).contiguous(), ir.to(torch.int64).contiguous()
+        pr = pr.to(torch.float64).contiguous()
+    else:
+        jc = np.ascontiguousarray(jc, dtype=np.int64)
+        ir = np.ascontiguousarray(ir, dtype=np.int64)
+        pr = np.ascontiguousarray(pr, dtype=np.float64)
+    if jc.ndim != 1 or jc.shape[0] != n + 1 or ir.ndim != 1 or ir.shape != pr.shape:
+        raise ValueError("jc has n + 1 entries; ir and pr are vectors of one length")
+    return jc, ir, pr, (M, n), any(dev)
+
+
+def synthesize(d, codes, grid, spatial_dims=2, crop=False, ctx=None):
+    """Reconstructions from sparse codes on the GPU (csrc/synth_codes.hip): the circular
+    convolutions ``sum_k d_k (*) z_k`` of every column of ``codes``, with the filters embedded
+    as the learners embed them (``circshift(padarray(d), -r)``).
+
+    ``d``: the learners' ``d_res``, ``[s, s, (s), channels..., K]``; ``codes``: the tuple
+    ``(jc, ir, pr, (M, n))`` of ``Session.codes_sparse`` / ``sparsify`` or a
+    scipy.sparse.csc_matrix, ``M = prod(grid) * K``; ``grid``: the ``spatial_dims`` (2 or 3)
+    extents the codes live on (``Session.grid()``).  Returns ``grid + d.shape[spatial_dims:-1]
+    + (n,)``; ``crop=True`` returns the interior ``[r : g - r]`` of every spatial axis -- the
+    4D learner's DZ, every objective's Dz.  NumPy codes go through ccsc_synthesize and a
+    Fortran-ordered NumPy array comes back; CUDA tensors go through ccsc_synthesize_dev and
+    everything stays on the device.  Each output element is one fma per contributing entry in
+    storage order: the result is bitwise reproducible and independent of the other columns.
+    ``ctx``: a one-device Context (default: a temporary one)."""
+    lib = L.lib()
+    jc, ir, pr, (M, n), on_dev = _codes_triple(codes)
+    if spatial_dims not in (2, 3) or len(grid) != spatial_dims:
+        raise ValueError("grid has spatial_dims (2 or 3) extents")
+    if d.ndim < spatial_dims + 1:
+        raise ValueError("d is [s, s, (s), channels..., K]")
+    dshape = tuple(int(v) for v in d.shape)
+    sp, chan, K = dshape[:spatial_dims], dshape[spatial_dims:-1], dshape[-1]
+    Cn = int(np.prod(chan, dtype=np.int64)) if chan else 1
+    g3 = tuple(int(v) for v in grid) + (1,) * (3 - spatial_dims)
+    ks3 = sp + (1,) * (3 - spatial_dims)
+    if M != g3[0] * g3[1] * g3[2] * K:
+        raise ValueError(f"codes have {M} rows; grid {tuple(grid)} with K = {K} has "
+                         f"{g3[0] * g3[1] * g3[2] * K}")
+    g_c, ks_c = (C.c_int32 * 3)(*g3), (C.c_int32 * 3)(*ks3)
+    nnz = int(ir.shape[0])
+    oshape = tuple(int(v) for v in grid) + chan + (n,)
+    own = ctx is None
+    eb = L.errbuf()
+    if on_dev:
+        import torch
+        device = pr.device
+        dt = d if hasattr(d, "is_cuda") else torch.from_numpy(np.asarray(d, dtype=np.float64))
+        dt = dt.to(device=device, dtype=torch.float64)
+        dcol = dt.permute(*reversed(range(dt.ndim))).contiguous()    # column-major memory
+        out = torch.empty(tuple(reversed(oshape)), dtype=torch.float64, device=device)
+        if own:
+            ctx = Context(device.index if device.index is not None
+                          else torch.cuda.current_device())
+        try:
+            torch.cuda.synchronize(device)
+            L.check(lib.ccsc_synthesize_dev(ctx.ptr, dcol.data_ptr(), ks_c, Cn, K, g_c,
+                                            jc.data_ptr(), ir.data_ptr(), pr.data_ptr(), n, nnz,
+                                            out.data_ptr(), eb, len(eb)), eb)
+        finally:
+            if own:
+                ctx.close()
+        out = out.permute(*reversed(range(out.ndim)))
+    else:
+        dh = np.asfortranarray(d, dtype=np.float64)
+        out = np.zeros(oshape, order="F")
+        if own:
+            import torch
+            ctx = Context(torch.cuda.current_device())
+        try:
+            L.check(lib.ccsc_synthesize(ctx.ptr, L.dptr(dh), ks_c, Cn, K, g_c, L.lptr(jc),
+                                        L.lptr(ir), L.dptr(pr), n, nnz, L.dptr(out), eb, len(eb)),
+                    eb)
+        finally:
+            if own:
+                ctx.close()
+    if crop:
+        out = out[tuple(slice(s // 2, gg - s // 2) for s, gg in zip(sp, grid))]
+    return out
+
+
+def densify(codes, ctx=None):
+    """The inverse of ``sparsify`` on the GPU: the dense ``[M, n]`` float64 matrix of the
+    tuple ``(jc, ir, pr, (M, n))`` or scipy.sparse matrix ``codes``, every entry bit for bit,
+    zeros elsewhere.  Rows must be strictly ascending inside a column (``CCSCError`` with
+    CCSC_E_INVALID otherwise).  NumPy in, Fortran-ordered NumPy out (ccsc_densify); CUDA
+    tensors in, a CUDA tensor out (ccsc_densify_dev)."""
+    lib = L.lib()
+    jc, ir, pr, (M, n), on_dev = _codes_triple(codes)
+    nnz = int(ir.shape[0])
+    own = ctx is None
+    eb = L.errbuf()
+    if on_dev:
+        import torch
+        device = pr.device
+        out = torch.empty((n, M), dtype=torch.float64, device=device)
+        if own:
+            ctx = Context(device.index if device.index is not None
+                          else torch.cuda.current_device())
+        try:
+            torch.cuda.synchronize(device)
+            L.check(lib.ccsc_densify_dev(ctx.ptr, jc.data_ptr(), ir.data_ptr(), pr.data_ptr(), M,
+                                         n, nnz, out.data_ptr(), eb, len(eb)), eb)
+        finally:
+            if own:
+                ctx.close()
+        return out.t()
+    out = np.zeros((M, n), order="F")
+    if own:
+        import torch
+        ctx = Context(torch.cuda.current_device())
+    try:
+        L.check(lib.ccsc_densify(ctx.ptr, L.lptr(jc), L.lptr(ir), L.dptr(pr), M, n, nnz,
+                                 L.dptr(out), eb, len(eb)), eb)
+    finally:
+        if own:
+            ctx.close()
+    return out
 
 
 def _learn_2d(variant, b, kernel_size, lambda_residual, lambda_prior, max_it, tol, verbose, init,

@@ -504,6 +504,72 @@ int32_t ccsc_test_codes_index(int64_t M, int64_t tile, int32_t wave, int32_t ste
                               int64_t tile_off, int64_t before, int32_t prefix, int64_t* out4,
                               char* err, size_t errlen);
 
+/* Synthesis from sparse codes: the reconstructions sum_k d_k (*) z_k of the columns of a
+ * compressed sparse column matrix (the triple of ccsc_session_codes_* / ccsc_sparsify_*), as a
+ * direct sparse convolution on the GPU.
+ *   g  = (X, Y, T), T = 1 for two spatial dimensions; ks = (s0, s1, s2), odd, 1 <= ks[i] <= g[i]
+ *        (s2 = 1 when T = 1), radii r_i = ks[i] / 2; C >= 1 channels, K >= 1 filters.
+ *   d  : column-major [s0, s1, s2, C, K] -- the learners' d_res as it is: 2D [s,s,K] and 3D
+ *        [s,s,s,K] have C = 1, 4D [s,s,U,V,K] has C = U V, 2-3D [s,s,W,K] has C = W.
+ *   jc[n + 1], ir[nnz], pr[nnz] : int64 / int64 / double, 0-based, M = X Y T K rows; row
+ *        x + X (y + Y (t + T k)) is code k at (x, y, t), the index the session entries emit.
+ *   out: column-major [X, Y, T, C, n],
+ *        out[x,y,t,c,j] = sum over the entries e of column j, in storage order,
+ *                         pr[e] * d[i0, i1, i2, c, k_e],  i_a = (p_a - p_a(e) + r_a) mod g_a,
+ *        an entry contributing only when i_a < ks[a] on every axis.
+ * That is the circular convolution with the filter embedded the way the learners embed it:
+ * padarray(d, size_x - ks, 0, 'post') then circshift by -r (2D/admm_learn_conv2D_large_
+ * dParallel.m:38-39; the products and sums over k it stands for: the same file :193,
+ * 3D/admm_learn_conv3D_large.m:218-224, 4D/admm_learn_conv4D_lightfield.m:205-206,
+ * 2-3D/DictionaryLearning/admm_learn.m:326-343).  The sessions' DZ is a different quantity:
+ * it is formed from dup{1}, the spectrum the last d-solve left (:193), which is not the
+ * spectrum of the d_res that is returned, and from the full codes, not the thresholded ones.
+ * Each output element starts at +0.0 and takes one fma(value, tap, acc) per contributing
+ * entry in the column's storage order (for a session's matrix: ascending k, t, y, x); there
+ * are no floating-point atomics, so a column's result is the same bits whatever else is in
+ * the call, however the host form chunks the columns, and when the column is taken alone.
+ * Rows need not be sorted or unique: duplicates add.
+ * One-device context only; ordered on the context's stream and synchronised on return.
+ * Every argument is validated before the device is touched: CCSC_E_INVALID for a NULL array,
+ * an even or non-positive ks[i], ks[i] > g[i], C, K or g[i] < 1, n < 0 or nnz < 0;
+ * CCSC_E_UNSUPPORTED for M >= 2^31 and for filters of 2^31 values or more (C K s0 s1 s2; the
+ * taps are read from device memory, so this is the only filter budget).  n == 0 is CCSC_OK
+ * and writes nothing; nnz == 0 gives zeros.  A malformed matrix reaches no memory: a column
+ * range outside [0, nnz] or decreasing and a row outside [0, M) are skipped on the device and
+ * the call returns CCSC_E_INVALID (out is then unspecified); the host form also checks jc
+ * before any launch.  The host form takes host arrays and stages columns in chunks that keep
+ * the device staging (16 B per entry, the chunk's output planes) within 256 MiB, a single
+ * column that needs more getting its own; CCSC_CODES_WS_MB=<MiB> lowers that budget (0: one
+ * column per chunk).  The _dev form takes every array on the context's device.  Workspace is
+ * allocated inside the call and freed before it returns (ccsc_plan_bytes is unchanged). */
+int32_t ccsc_synthesize(ccsc_ctx* ctx, const double* d, const int32_t* ks, int32_t C, int32_t K,
+                        const int32_t* g, const int64_t* jc, const int64_t* ir, const double* pr,
+                        int64_t n, int64_t nnz, double* out, char* err, size_t errlen);
+int32_t ccsc_synthesize_dev(ccsc_ctx* ctx, const double* d, const int32_t* ks, int32_t C,
+                            int32_t K, const int32_t* g, const int64_t* jc, const int64_t* ir,
+                            const double* pr, int64_t n, int64_t nnz, double* out, char* err,
+                            size_t errlen);
+/* The inverse of ccsc_sparsify_*: out, column-major [M, n], is zero-filled and every entry is
+ * stored at its row, bit for bit.  Rows must be strictly ascending inside a column (no two
+ * entries may meet); a column that breaks this, a column range outside [0, nnz] and a row
+ * outside [0, M) are skipped and the call returns CCSC_E_INVALID.  Validation, context,
+ * chunking (8 M bytes of output and 16 B per entry per column) as for ccsc_synthesize. */
+int32_t ccsc_densify(ccsc_ctx* ctx, const int64_t* jc, const int64_t* ir, const double* pr,
+                     int64_t M, int64_t n, int64_t nnz, double* out, char* err, size_t errlen);
+int32_t ccsc_densify_dev(ccsc_ctx* ctx, const int64_t* jc, const int64_t* ir, const double* pr,
+                         int64_t M, int64_t n, int64_t nnz, double* out, char* err,
+                         size_t errlen);
+/* Host only: the index arithmetic of k_synth_codes, for grids whose row count reaches 2^31 - 1.
+ * For row `row` of a [g, K] code volume, the output tile [lo, lo + len) per axis, the output
+ * point p, channel c and column col: out8 = {x, y, t, k of the row; 1 if the entry lies in
+ * the tile's source window (the tile grown by r, circularly); the index into d of the tap
+ * that carries the entry to p, or -1 if p is outside the entry's footprint; the index into
+ * out of (p, c, col); M}. */
+int32_t ccsc_test_synth_index(const int32_t* g, const int32_t* ks, int32_t C, int32_t K,
+                              int64_t row, const int32_t* lo, const int32_t* len,
+                              const int32_t* p, int32_t c, int64_t col, int64_t* out8, char* err,
+                              size_t errlen);
+
 /* ---- kernel-level entry points (parity tests of single stages) ---------- */
 /* 2D R2C of `count` real slices [X,Y] -> half spectra [Y][X/2+1] (re,im). */
 int32_t ccsc_test_fft2d(ccsc_ctx* ctx, int32_t X, int32_t Y, int32_t count, const double* in,
