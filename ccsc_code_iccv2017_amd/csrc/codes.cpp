@@ -162,7 +162,7 @@ static void sparsify_count_host(ccsc_ctx* ctx, const double* a, int64_t M, int64
     const int64_t m = std::min(chunk, n - c0);
     HIPCHK(hipMemcpyAsync(in.p, a + c0 * M, (size_t)(m * M) * 8, hipMemcpyHostToDevice,
                           ctx->stream));
-    codes_count_dev(ctx, in.as<double>(), M, m, eps, jc + c0);
+    codes_count_dev(ctx, in.re(), M, m, eps, jc + c0);
   }
 }
 
@@ -233,7 +233,7 @@ int32_t ccsc_sparsify_fill(ccsc_ctx* ctx, const double* a, int64_t M, int64_t n,
       if (!once)
         HIPCHK(hipMemcpyAsync(in.p, a + c0 * M, (size_t)(m * M) * 8, hipMemcpyHostToDevice,
                               ctx->stream));
-      codes_fill_dev(ctx, in.as<double>(), M, m, eps, h.data() + c0, ir, pr, false);
+      codes_fill_dev(ctx, in.re(), M, m, eps, h.data() + c0, ir, pr, false);
     }
   });
 }

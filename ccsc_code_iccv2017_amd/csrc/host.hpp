@@ -1,18 +1,16 @@
-// Host-side helpers shared by the libccsc translation units (engine.cpp, solve.cpp):
-// error type and guards of the C-ABI, HIP/RCCL checks, device buffers, the context.
+// Host-side helpers shared by the libccsc translation units: error type and guards of the
+// C-ABI, HIP/RCCL checks, device buffers, the global line passes, the context.
 #pragma once
 
 #include "../../include/ccsc.h"
+#include "comm.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
 #include <rccl/rccl.h>
 
-#include <atomic>
-#include <condition_variable>
 #include <cstdio>
 #include <memory>
-#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -77,13 +75,15 @@ struct DevBuf {
     bytes = 0;
   }
   template <typename X> X* as() const { return reinterpret_cast<X*>(p); }
+  double* re() const { return as<double>(); }             // the engine is fp64 only
+  cpx<double>* cx() const { return as<cpx<double>>(); }
 };
 
 // a twiddle table onto the device (into b, allocated here unless a memory plan already did)
 inline const cpx<double>* upload_twiddles(DevBuf& b, const std::vector<cpx<double>>& t) {
   if (!b.p) b.alloc(t.size() * sizeof(cpx<double>));
   HIPCHK(hipMemcpy(b.p, t.data(), t.size() * sizeof(cpx<double>), hipMemcpyHostToDevice));
-  return b.as<cpx<double>>();
+  return b.cx();
 }
 
 // The global line passes of one grid (recon.hip) on a stream: their twiddle tables on the
@@ -128,75 +128,6 @@ struct LinePass {
   }
 };
 
-}  // namespace ccsc
-
-namespace ccsc {
-// In-process exchange between the device threads of a multi-device context whose
-// device list repeats a device (RCCL needs distinct GPUs): every rank deposits its
-// buffer, the last to arrive combines them in rank order (deterministic sums) and
-// releases the others.  abort() wakes every waiter when one device thread failed.
-struct HostGroup {
-  int n;
-  std::mutex mu;
-  std::condition_variable cv;
-  int arrived = 0;
-  uint64_t gen = 0;
-  bool aborted = false;
-  std::vector<std::vector<double>> slot;
-  std::vector<double> res;
-  explicit HostGroup(int n_) : n(n_), slot(n_) {}
-  int exchange(int rank, int op, double* buf, int64_t count) {
-    std::unique_lock<std::mutex> lk(mu);
-    if (aborted) return -1;
-    const uint64_t g = gen;
-    slot[rank].assign(buf, buf + count);
-    if (++arrived == n) {
-      if (op == CCSC_COMM_BCAST0) {
-        res = slot[0];
-      } else {
-        res = slot[0];
-        for (int r = 1; r < n; ++r)
-          for (int64_t i = 0; i < count; ++i) res[i] += slot[r][i];
-      }
-      arrived = 0;
-      ++gen;
-      cv.notify_all();
-    } else {
-      cv.wait(lk, [&] { return gen != g || aborted; });
-      if (aborted) return -1;
-    }
-    // the next exchange cannot complete (and replace res) before every rank has
-    // arrived at it, i.e. has copied this result
-    std::copy(res.begin(), res.begin() + count, buf);
-    return 0;
-  }
-  void abort() {
-    std::lock_guard<std::mutex> lk(mu);
-    aborted = true;
-    cv.notify_all();
-  }
-};
-struct HostGroupRank {
-  HostGroup* g;
-  int rank;
-};
-static int32_t host_group_fn(void* user, int32_t op, double* buf, int64_t count) {
-  auto* u = static_cast<HostGroupRank*>(user);
-  return u->g->exchange(u->rank, op, buf, count);
-}
-
-// Failure state shared by the ranks of a multi-device context.  When one rank's
-// thread fails, abort_group() (engine.cpp) marks the group aborted ONCE, wakes the
-// in-process exchange and aborts every RCCL communicator, so the other ranks' blocked
-// collectives return; every later collective of the group throws instead of touching
-// a communicator.  `inflight` counts collectives between that check and their
-// enqueue, so the abort does not free a communicator under them.  The next
-// ccsc_learn on the context re-creates the communicators (reset_group).
-struct CommGroup {
-  std::mutex mu;
-  std::atomic<bool> aborted{false};
-  std::atomic<int> inflight{0};
-};
 }  // namespace ccsc
 
 struct ccsc_ctx {

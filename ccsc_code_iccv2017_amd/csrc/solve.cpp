@@ -124,8 +124,8 @@ struct Solver {
 
   // both spectrum sets (codes, data) in one launch per line direction
   void cols2(int sign, int64_t nz, int64_t nx) {
-    cpx<double>* a = Sz.as<cpx<double>>();
-    cpx<double>* b = Sx.as<cpx<double>>();
+    cpx<double>* a = Sz.cx();
+    cpx<double>* b = Sx.cx();
     auto y_lines = [&] {
       HIPCHK(launch_cols<double>(a, sign, nz * S.Tn, S.lp.cy, lines.twy, st, b, nx * S.Tn));
     };
@@ -165,10 +165,10 @@ struct Solver {
       HIPCHK(hipMemcpyAsync(kd.p, hk.data(), kd.bytes, hipMemcpyHostToDevice, st));
       grid.alloc((size_t)(nfilt * P) * 8);
       HIPCHK(hipMemsetAsync(grid.p, 0, grid.bytes, st));
-      HIPCHK(launch_embed_kernels<double>(kd.as<double>(), grid.as<double>(), kx, ky, kt,
+      HIPCHK(launch_embed_kernels<double>(kd.re(), grid.re(), kx, ky, kt,
                                           (int)nfilt, S.X, S.Y, S.Tn, st));
       dhat.alloc((size_t)(nfilt * F) * 16);
-      lines.r2c(grid.as<double>(), dhat.as<cpx<double>>(), nfilt);
+      lines.r2c(grid.re(), dhat.cx(), nfilt);
       if (v3) {
         // dhat = psf_hat .* dhat_k (SV:131); the reconstruction keeps dhat_k (SV:109)
         dhat_res.alloc(dhat.bytes);
@@ -179,11 +179,11 @@ struct Solver {
         HIPCHK(hipMemcpyAsync(pd.p, in.psf, pd.bytes, hipMemcpyHostToDevice, st));
         pg.alloc((size_t)P * 8);
         HIPCHK(hipMemsetAsync(pg.p, 0, pg.bytes, st));
-        HIPCHK(launch_embed_kernels<double>(pd.as<double>(), pg.as<double>(), p.psf_size[0],
+        HIPCHK(launch_embed_kernels<double>(pd.re(), pg.re(), p.psf_size[0],
                                             p.psf_size[1], p.psf_size[2], 1, S.X, S.Y, S.Tn, st));
         ph.alloc((size_t)F * 16);
-        lines.r2c(pg.as<double>(), ph.as<cpx<double>>(), 1);
-        HIPCHK(launch_spec_mul<double>(dhat.as<cpx<double>>(), ph.as<cpx<double>>(), F, (int)nfilt, st));
+        lines.r2c(pg.re(), ph.cx(), 1);
+        HIPCHK(launch_spec_mul<double>(dhat.cx(), ph.cx(), F, (int)nfilt, st));
         HIPCHK(hipStreamSynchronize(st));
       }
       HIPCHK(hipStreamSynchronize(st));
@@ -191,7 +191,7 @@ struct Solver {
     // s = sum |dhat|^2 (SI:166); the diagonal solves keep invP / (rho + s) (SD:132, SV:155)
     senergy.alloc((size_t)F * 8);
     const bool diag = p.variant == CCSC_SOLVE_MULTICH || v3;
-    HIPCHK(launch_spec_energy<double>(dhat.as<cpx<double>>(), senergy.as<double>(), F, (int)nfilt,
+    HIPCHK(launch_spec_energy<double>(dhat.cx(), senergy.re(), F, (int)nfilt,
                                       diag ? 1 : 0, S.rho, 1.0 / (double)P, st));
     // ---- per-image data on the padded grid
     const int64_t sbv = p.sb[0] * p.sb[1] * p.sb[2];
@@ -214,18 +214,15 @@ struct Solver {
       Mb.alloc(M.bytes);
       if (has_sm) SM.alloc(M.bytes);
       if (psnr) XO.alloc(M.bytes);
-      HIPCHK(launch_pad_inputs<double>(b.as<double>(), mk.as<double>(), sm.as<double>(),
-                                       xo.as<double>(), M.as<double>(), Mb.as<double>(),
-                                       SM.as<double>(), XO.as<double>(), nd, (int)p.sb[0],
-                                       (int)p.sb[1], (int)p.sb[2], S.rx, S.ry, S.rt, S.X, S.Y,
-                                       S.Tn, st));
+      HIPCHK(launch_pad_inputs<double>(b.re(), mk.re(), sm.re(), xo.re(), M.re(), Mb.re(), SM.re(),
+                                       XO.re(), nd, (int)p.sb[0], (int)p.sb[1], (int)p.sb[2], S.rx,
+                                       S.ry, S.rt, S.X, S.Y, S.Tn, st));
       // gamma_heuristic = c * lambda / max(b(:)) per image (SI:36)
       DevBuf scratch, mx;
       scratch.alloc(2 * kNormParts * 8);
       mx.alloc((size_t)n * 8);
       for (int64_t i = 0; i < n; ++i)
-        HIPCHK(launch_max<double>(b.as<double>() + i * W * sbv, W * sbv, scratch.as<double>(),
-                                  mx.as<double>() + i, st));
+        HIPCHK(launch_max<double>(b.re() + i * W * sbv, W * sbv, scratch.re(), mx.re() + i, st));
       std::vector<double> hmax((size_t)n);
       HIPCHK(hipMemcpyAsync(hmax.data(), mx.p, mx.bytes, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
@@ -260,14 +257,14 @@ struct Solver {
 
   RowArgs<double> code_args(bool first) {
     RowArgs<double> a{};
-    a.S = Sz.as<cpx<double>>();
-    a.Z = Z.as<double>();
-    a.D = D2.as<double>();
-    a.part = part.as<double>();
+    a.S = Sz.cx();
+    a.Z = Z.re();
+    a.D = D2.re();
+    a.part = part.re();
     a.part_slices = S.Kc + S.W;
     a.part_off = 0;
     a.active = active.as<int>();
-    a.theta = theta2.as<double>();
+    a.theta = theta2.re();
     a.per_img = S.Kc;
     a.first = first ? 1 : 0;
     a.prox = S.p.variant == CCSC_SOLVE_POISSON2D ? 1 : 0;
@@ -277,16 +274,16 @@ struct Solver {
   RowArgs<double> data_args(bool first) {
     const ccsc_solve_problem& p = S.p;
     RowArgs<double> a{};
-    a.S = Sx.as<cpx<double>>();
-    a.D = D1.as<double>();
-    a.M = M.as<double>();
-    a.Mb = Mb.as<double>();
-    a.SM = SM.p ? SM.as<double>() : nullptr;
-    a.XO = XO.p ? XO.as<double>() : nullptr;
-    a.part = part.as<double>();
+    a.S = Sx.cx();
+    a.D = D1.re();
+    a.M = M.re();
+    a.Mb = Mb.re();
+    a.SM = SM.p ? SM.re() : nullptr;
+    a.XO = XO.p ? XO.re() : nullptr;
+    a.part = part.re();
     a.part_slices = S.Kc + S.W;
     a.part_off = S.Kc;
-    a.theta = theta1.as<double>();
+    a.theta = theta1.re();
     a.per_img = S.W;
     a.first = first ? 1 : 0;
     a.prox = p.variant == CCSC_SOLVE_POISSON2D ? 1 : 0;
@@ -306,18 +303,15 @@ struct Solver {
     const ccsc_solve_problem& p = S.p;
     const double invP = 1.0 / (double)S.P;
     if (p.variant == CCSC_SOLVE_INPAINT2D || p.variant == CCSC_SOLVE_POISSON2D) {
-      HIPCHK(launch_solve_sm<double>(Sz.as<cpx<double>>(), Sx.as<cpx<double>>(),
-                                     dhat.as<cpx<double>>(), senergy.as<double>(), S.rho, invP,
+      HIPCHK(launch_solve_sm<double>(Sz.cx(), Sx.cx(), dhat.cx(), senergy.re(), S.rho, invP,
                                      (int)S.F, S.Kc, n, p.variant == CCSC_SOLVE_POISSON2D ? 1 : 0,
                                      S.X, S.Y, S.X / 2 + 1, st));
     } else {
       // zhat_k = (sum_w conj(dhat_wk) xi1_w + rho xi2_k) * invP / (rho + s), then
       // v1_w = sum_k dhat_wk zhat_k: the per-bin GEMMs of hs23.hip (dhat [K][W][F])
-      HIPCHK(launch_hs_analysis<double>(dhat.as<cpx<double>>(), Sx.as<cpx<double>>(),
-                                        Sz.as<cpx<double>>(), senergy.as<double>(), S.rho,
-                                        Sz.as<cpx<double>>(), (int)S.F, S.W, S.Kc, (int)n, st));
-      HIPCHK(launch_hs_synth<double>(dhat.as<cpx<double>>(), Sz.as<cpx<double>>(),
-                                     Sx.as<cpx<double>>(), (int)S.F, S.W, S.Kc, (int)n, st));
+      HIPCHK(launch_hs_analysis<double>(dhat.cx(), Sx.cx(), Sz.cx(), senergy.re(), S.rho, Sz.cx(),
+                                        (int)S.F, S.W, S.Kc, (int)n, st));
+      HIPCHK(launch_hs_synth<double>(dhat.cx(), Sz.cx(), Sx.cx(), (int)S.F, S.W, S.Kc, (int)n, st));
     }
   }
 
@@ -347,7 +341,7 @@ struct Solver {
       HIPCHK(launch_rows_pair<double>(last ? kRowFinalZ : kRowIterZ, code_args(i == 0), nz,
                                       data_args(i == 0), nx, S.lp.rg, lines.twr, st));
       if (need_sums) {
-        HIPCHK(launch_reduce_parts<double>(part.as<double>(), sums.as<double>(), n, S.Kc + S.W,
+        HIPCHK(launch_reduce_parts<double>(part.re(), sums.re(), n, S.Kc + S.W,
                                            S.lp.rg.groups, st));
         HIPCHK(hipMemcpyAsync(hs.data(), sums.p, sums.bytes, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -400,14 +394,13 @@ struct Solver {
     if (out && out->z)
       HIPCHK(hipMemcpyAsync(out->z, Z.p, Z.bytes, hipMemcpyDeviceToHost, st));
     if (out && out->res) {
-      lines.r2c(Z.as<double>(), Sz.as<cpx<double>>(), nz);
-      const cpx<double>* dres = dhat_res.p ? dhat_res.as<cpx<double>>() : dhat.as<cpx<double>>();
-      HIPCHK(launch_hs_synth<double>(dres, Sz.as<cpx<double>>(), Sx.as<cpx<double>>(), (int)S.F,
-                                     S.W, S.Kc, (int)n, st));
-      lines.inv_cols(Sx.as<cpx<double>>(), nx);
+      lines.r2c(Z.re(), Sz.cx(), nz);
+      const cpx<double>* dres = dhat_res.p ? dhat_res.cx() : dhat.cx();
+      HIPCHK(launch_hs_synth<double>(dres, Sz.cx(), Sx.cx(), (int)S.F, S.W, S.Kc, (int)n, st));
+      lines.inv_cols(Sx.cx(), nx);
       RowArgs<double> a{};
-      a.S = Sx.as<cpx<double>>();
-      a.SM = SM.p ? SM.as<double>() : nullptr;
+      a.S = Sx.cx();
+      a.SM = SM.p ? SM.re() : nullptr;
       a.per_img = S.W;
       a.Y = S.Y;
       a.sbx = (int)p.sb[0];
@@ -420,7 +413,7 @@ struct Solver {
       a.scale = 1.0 / (double)S.P;
       DevBuf res;
       res.alloc((size_t)(nx * p.sb[0] * p.sb[1] * p.sb[2]) * 8);
-      a.res = res.as<double>();
+      a.res = res.re();
       HIPCHK(launch_rows<double>(kRowRes, a, nx, S.lp.rg, lines.twr, st));
       HIPCHK(hipMemcpyAsync(out->res, res.p, res.bytes, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
@@ -614,7 +607,7 @@ int32_t ccsc_local_cn(ccsc_ctx* ctx, const double* in, double* out, int64_t n, i
       const int64_t m = std::min(chunk, n - i0);
       HIPCHK(hipMemcpyAsync(a.p, in + i0 * per, (size_t)(m * per) * 8, hipMemcpyHostToDevice,
                             ctx->stream));
-      local_cn_device(ctx, a.as<double>(), b.as<double>(), m, H, W);
+      local_cn_device(ctx, a.re(), b.re(), m, H, W);
       HIPCHK(hipMemcpyAsync(out + i0 * per, b.p, (size_t)(m * per) * 8, hipMemcpyDeviceToHost,
                             ctx->stream));
     }
@@ -631,7 +624,7 @@ int32_t ccsc_imfilter_dev(ccsc_ctx* ctx, const double* in, double* out, int64_t 
     HIPCHK(hipSetDevice(ctx->device));
     DevBuf taps;
     imfilter_taps(S, k, taps);
-    HIPCHK(launch_imfilter(in, out, n, S.dims, taps.as<double>(), S.kdims, boundary, ctx->stream));
+    HIPCHK(launch_imfilter(in, out, n, S.dims, taps.re(), S.kdims, boundary, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));   // the taps are released on return
   });
 }
@@ -652,8 +645,7 @@ int32_t ccsc_imfilter(ccsc_ctx* ctx, const double* in, double* out, int64_t n, i
       const int64_t m = std::min(chunk, n - i0);
       HIPCHK(hipMemcpyAsync(a.p, in + i0 * S.per, (size_t)(m * S.per) * 8, hipMemcpyHostToDevice,
                             ctx->stream));
-      HIPCHK(launch_imfilter(a.as<double>(), b.as<double>(), m, S.dims, taps.as<double>(), S.kdims,
-                             boundary, ctx->stream));
+      HIPCHK(launch_imfilter(a.re(), b.re(), m, S.dims, taps.re(), S.kdims, boundary, ctx->stream));
       HIPCHK(hipMemcpyAsync(out + i0 * S.per, b.p, (size_t)(m * S.per) * 8, hipMemcpyDeviceToHost,
                             ctx->stream));
     }
@@ -699,7 +691,7 @@ int32_t ccsc_nn_fill(ccsc_ctx* ctx, const double* in, const double* known, doubl
       HIPCHK(hipMemcpyAsync(a.p, in + i0 * per, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
       if (known)
         HIPCHK(hipMemcpyAsync(k.p, known + i0 * per, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(launch_nn_fill(a.as<double>(), k.as<double>(), a.as<double>(), ix.as<int>(),
+      HIPCHK(launch_nn_fill(a.re(), k.re(), a.re(), ix.as<int>(),
                             r.as<int>(), m, H, W, ctx->stream));
       HIPCHK(hipMemcpyAsync(out + i0 * per, a.p, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
       if (idx)
@@ -735,11 +727,11 @@ int32_t ccsc_standardize(ccsc_ctx* ctx, const double* in, double* out, double* m
     ws.alloc((size_t)standardize_ws_bytes(chunk, N));
     for (int64_t i0 = 0; i0 < planes; i0 += chunk) {
       const int64_t m = std::min(chunk, planes - i0);
-      double* dm = ms.as<double>();
+      double* dm = ms.re();
       double* ds = dm + chunk;
       HIPCHK(hipMemcpyAsync(a.p, in + i0 * N, (size_t)(m * N) * 8, hipMemcpyHostToDevice,
                             ctx->stream));
-      HIPCHK(launch_standardize(a.as<double>(), a.as<double>(), dm, ds, m, N, ws.p, ctx->stream));
+      HIPCHK(launch_standardize(a.re(), a.re(), dm, ds, m, N, ws.p, ctx->stream));
       HIPCHK(hipMemcpyAsync(out + i0 * N, a.p, (size_t)(m * N) * 8, hipMemcpyDeviceToHost,
                             ctx->stream));
       HIPCHK(hipMemcpyAsync(mean + i0, dm, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -774,13 +766,13 @@ int32_t ccsc_unstandardize(ccsc_ctx* ctx, const double* in, double* out, const d
     ms.alloc((size_t)chunk * 16);
     for (int64_t i0 = 0; i0 < planes; i0 += chunk) {
       const int64_t m = std::min(chunk, planes - i0);
-      double* dm = ms.as<double>();
+      double* dm = ms.re();
       double* ds = dm + chunk;
       HIPCHK(hipMemcpyAsync(a.p, in + i0 * N, (size_t)(m * N) * 8, hipMemcpyHostToDevice,
                             ctx->stream));
       HIPCHK(hipMemcpyAsync(dm, mean + i0, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
       HIPCHK(hipMemcpyAsync(ds, sdev + i0, (size_t)m * 8, hipMemcpyHostToDevice, ctx->stream));
-      HIPCHK(launch_unstandardize(a.as<double>(), a.as<double>(), dm, ds, m, N, ctx->stream));
+      HIPCHK(launch_unstandardize(a.re(), a.re(), dm, ds, m, N, ctx->stream));
       HIPCHK(hipMemcpyAsync(out + i0 * N, a.p, (size_t)(m * N) * 8, hipMemcpyDeviceToHost,
                             ctx->stream));
     }

@@ -119,7 +119,7 @@ void host_chunks(ccsc_ctx* ctx, const int64_t* jc, const int64_t* ir, const doub
   std::vector<int64_t> hj;
   for (int64_t c0 = 0; c0 < n;) {
     const int64_t c1 = chunk_end(c0), m = c1 - c0, kept = jc[c1] - jc[c0];
-    double* dout = ws.as<double>();
+    double* dout = ws.re();
     int64_t* dir = reinterpret_cast<int64_t*>(dout + m * col_elems);
     double* dpr = reinterpret_cast<double*>(dir + kept);
     int64_t* djc = reinterpret_cast<int64_t*>(dpr + kept);
@@ -193,7 +193,7 @@ int32_t ccsc_synthesize(ccsc_ctx* ctx, const double* d, const int32_t* ks, int32
     host_chunks(ctx, jc, ir, pr, n, col_elems, out,
                 [&](const int64_t* djc, const int64_t* dir, const double* dpr, int64_t m,
                     int64_t kept, double* dout) {
-                  HIPCHK(launch_synth_codes(G, dd.as<double>(), djc, dir, dpr, m, kept, dout,
+                  HIPCHK(launch_synth_codes(G, dd.re(), djc, dir, dpr, m, kept, dout,
                                             flag.b.as<int32_t>(), ctx->stream));
                 });
     flag.finish(ctx->stream);

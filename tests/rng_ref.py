@@ -10,7 +10,7 @@ Needs no GPU.
 """
 import numpy as np
 
-FILTER_SEED_XOR = 0xD0D0D0D0   # the filters' stream: seed ^ this (engine.cpp, Session2D / SessionHS)
+FILTER_SEED_XOR = 0xD0D0D0D0   # the filters' stream: seed ^ this (session2d.cpp / session_hs.cpp)
 
 _M1 = np.uint64(0xBF58476D1CE4E5B9)
 _M2 = np.uint64(0x94D049BB133111EB)

@@ -2,7 +2,7 @@
 split contiguously over ranks, ONE all-reduce of the support-restricted
 sum_j (D_j + y_j) per d-iteration and ONE broadcast of block 1's filter
 spectrum per outer iteration -- reproduces the single-process learner.  This is
-the exchange schedule the engine runs over RCCL (engine.cpp outer_iteration)."""
+the exchange schedule the engine runs over RCCL (session2d.cpp outer_iteration)."""
 import os
 import socket
 
@@ -85,7 +85,7 @@ def _hs_problem():
 
 
 def _hs_worker(rank, world, port, out_dir):
-    """The 2-3D learner's rank exchange (engine.cpp SessionHS, dist): each rank forms the
+    """The 2-3D learner's rank exchange (session_hs.cpp SessionHS, dist): each rank forms the
     per-frequency Gram Z_r^H Z_r of its images (+ rho I on rank 0 only) and the right-hand
     sides Z_r^H xi1_r, both summed over the ranks; every rank solves the same system."""
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -93,7 +93,7 @@ def _hs_worker(rank, world, port, out_dir):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     zh, x1, x2, rho = _hs_problem()
     X, Y, W, K, n = zh.shape[0], zh.shape[1], x1.shape[2], zh.shape[3], zh.shape[4]
-    base, rem = divmod(n, world)                      # engine.cpp shard(): contiguous images
+    base, rem = divmod(n, world)                      # plan.cpp shard(): contiguous images
     nl = base + (1 if rank < rem else 0)
     i0 = rank * base + min(rank, rem)
     Z = zh[:, :, 0, :, i0:i0 + nl].reshape(X * Y, K, nl, order="F").transpose(0, 2, 1)  # [f, p, k]

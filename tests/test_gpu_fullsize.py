@@ -55,7 +55,7 @@ def test_c1_fullsize_20_iterations(gpu_ctx):
     """C1 at full size (2D dParallel, K = 100 11x11, n = 1000, ni = 100 -> 10 blocks) for
     the reference driver's 20 outer iterations: the iteration-0 objective matches its
     closed form for the random init, the objective decreases, and the learned filters
-    sit on the unit sphere (1000 patches take the two-stream z-phase, engine.cpp
+    sit on the unit sphere (1000 patches take the two-stream z-phase, session2d.cpp
     zsplit_ok)."""
     from ccsc_code_iccv2017_amd import learners as E
     from ccsc_code_iccv2017_amd import synth

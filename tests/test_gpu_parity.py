@@ -695,7 +695,7 @@ def test_zline_tol_matches_port(gpu_ctx, variant, verbose):
 @pytest.mark.parametrize("variant", ["dZ", "dP"])
 def test_zline_two_stream_phase_is_exact(gpu_ctx, monkeypatch, variant):
     """With tol = 0 and >= 512 patches on the 110 grid the engine splits every z-launch of a
-    phase over two streams (patches [0, np/2) and the rest, engine.cpp zsplit_ok); the
+    phase over two streams (patches [0, np/2) and the rest, session2d.cpp zsplit_ok); the
     per-patch arithmetic is the same kernel's, so the result equals the one-stream run
     bit for bit -- for dZ (the bench workload) and dP (C1's 1000 patches take this path)."""
     from ccsc_code_iccv2017_amd import learners as E
