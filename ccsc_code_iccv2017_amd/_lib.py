@@ -241,6 +241,16 @@ SIGNATURES = {
     "ccsc_test_synth_index": (C.c_int32, [_ip, _ip, C.c_int32, C.c_int32, C.c_int64, _ip, _ip,
                                           _ip, C.c_int32, C.c_int64, _lp, C.c_char_p,
                                           C.c_size_t]),
+    "ccsc_threshold_sweep": (C.c_int32, [C.c_void_p, _dp, _ip, C.c_int32, C.c_int32, _ip, _lp,
+                                         _lp, _dp, C.c_int64, C.c_int64, _dp, C.c_int32, _dp,
+                                         C.c_int32, _lp, _dp, _dp, C.c_char_p, C.c_size_t]),
+    "ccsc_threshold_sweep_dev": (C.c_int32, [C.c_void_p, C.c_void_p, _ip, C.c_int32, C.c_int32,
+                                             _ip, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                             C.c_int64, C.c_void_p, C.c_int32, _dp, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p,
+                                             C.c_size_t]),
+    "ccsc_test_sweep_class": (C.c_int32, [_dp, C.c_int32, C.c_double, _ip, C.c_char_p,
+                                          C.c_size_t]),
     "ccsc_test_fft2d": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
                                     C.c_char_p, C.c_size_t]),
     "ccsc_test_fft_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32,

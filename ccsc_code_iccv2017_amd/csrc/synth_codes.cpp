@@ -7,18 +7,18 @@
 // 0: one column per chunk); a single column that needs more gets its own.  The filters go
 // up once.  Everything is allocated here and freed before the call returns.  A column's
 // result does not depend on the chunk it travels in.
-#include "synth_codes.hpp"
-#include "host.hpp"
+#include "synth_host.hpp"
 
 #include <algorithm>
 #include <cstring>
 
 namespace ccsc {
-namespace {
 
-const char* kMalformed =
+const char* const kCscMalformed =
     "the sparse matrix is malformed: a column range of jc outside [0, nnz] or decreasing, or a "
     "row of ir outside [0, M)";
+
+namespace {
 
 void check_csc_args(const int64_t* jc, const int64_t* ir, const double* pr, int64_t n,
                     int64_t nnz, const double* out, bool need_out) {
@@ -29,6 +29,8 @@ void check_csc_args(const int64_t* jc, const int64_t* ir, const double* pr, int6
   if (nnz > 0 && !pr) throw Err(CCSC_E_INVALID, "NULL pr");
   if (!out && need_out) throw Err(CCSC_E_INVALID, "NULL out");
 }
+
+}  // namespace
 
 SynthGeom synth_check(const double* d, const int32_t* ks, int32_t C, int32_t K, const int32_t* g,
                       const int64_t* jc, const int64_t* ir, const double* pr, int64_t n,
@@ -83,20 +85,9 @@ void check_jc_host(const int64_t* jc, int64_t n, int64_t nnz) {
                                   std::to_string(nnz));
 }
 
-struct Flag {
-  DevBuf b;
-  void reset(hipStream_t st) {
-    b.alloc(sizeof(int32_t));
-    HIPCHK(hipMemsetAsync(b.p, 0, sizeof(int32_t), st));
-  }
-  // synchronises the stream; CCSC_E_INVALID when a kernel raised the flag
-  void finish(hipStream_t st) {
-    int32_t h = 0;
-    HIPCHK(hipMemcpyAsync(&h, b.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (h != 0) throw Err(CCSC_E_INVALID, kMalformed);
-  }
-};
+namespace {
+
+using Flag = CscFlag;
 
 // Host triple -> host output [col_elems, n] through launch(jc, ir, pr, m, kept, out) on device
 // copies of chunks of columns; jc has passed check_jc_host.
@@ -221,7 +212,7 @@ int32_t ccsc_densify(ccsc_ctx* ctx, const int64_t* jc, const int64_t* ir, const 
     densify_check(jc, ir, pr, M, n, nnz, out);
     check_ctx(ctx, "densify");
     check_jc_host(jc, n, nnz);
-    if (M == 0 && jc[n] > jc[0]) throw Err(CCSC_E_INVALID, kMalformed);
+    if (M == 0 && jc[n] > jc[0]) throw Err(CCSC_E_INVALID, kCscMalformed);
     if (n == 0 || M == 0) return;
     HIPCHK(hipSetDevice(ctx->device));
     Flag flag;

@@ -28,6 +28,9 @@ compressed sparse column tuple ``(jc, ir, pr, (M, n))`` of ``Session.codes_spars
 device-list context raises ``CCSCError`` (sessions run on a one-device context).
 ``synthesize(d_res, codes, grid)`` reconstructs ``sum_k d_k (*) z_k`` from such a tuple on
 the GPU and ``densify(codes)`` expands it; ``sparsify`` makes one from any dense matrix.
+``threshold_sweep(d_res, codes, b, eps_list, grid)`` (``Session.threshold_sweep``) returns,
+per candidate threshold and patch, the surviving entries, their l1 mass and the squared error
+of the reconstruction against ``b`` in one pass; ``pick_eps`` chooses among them.
 
 Errors are raised as ``CCSCError`` (the MATLAB reference raises on bad shapes
 too; ``n % ni != 0`` is an error here rather than a silent floor, Q13).
@@ -333,6 +336,31 @@ class Session:
             return csc_matrix((pr, ir, jc), shape=shape)
         return jc, ir, pr, shape
 
+    def data(self):
+        """The local patches' data as the objective compares it with Dz: the interior-cropped
+        ``b`` of this rank's columns (2-3D: ``b - smooth_init``), Fortran-ordered."""
+        j0 = self.block_begin * (1 if self.p.variant == L.CCSC_HS23 else self.p.ni)
+        sl = (Ellipsis, slice(j0, j0 + self.n_local))
+        b = self._b[sl] - self._sm[sl] if self.p.variant == L.CCSC_HS23 else self._b[sl]
+        return np.asfortranarray(b)
+
+    def threshold_sweep(self, eps):
+        """``threshold_sweep`` of the session's own filters, codes and data: ``results()``'s
+        d_res, ``codes_sparse(min(eps))`` (so every threshold is >= 0) and ``data()``, the
+        views of the 4D learner and the bands of the 2-3D learner as channels.  Returns the
+        dict of ``learners.threshold_sweep`` with ``[E, n_local]`` NumPy arrays; the session
+        is left as ``results(want_z=True)`` leaves it."""
+        ev = np.atleast_1d(np.asarray(eps, dtype=np.float64))
+        if ev.ndim != 1 or ev.size < 1:
+            raise ValueError("eps is one threshold or a non-empty vector of them")
+        if np.isnan(ev).any():
+            raise ValueError("a threshold is NaN")
+        d_res = self.results(want_z=False, want_DZ=False)[0]
+        codes = self.codes_sparse(float(ev.min()))
+        grid = self.grid()
+        return threshold_sweep(d_res, codes, self.data(), ev, grid, spatial_dims=len(grid),
+                               ctx=self.ctx)
+
     def iterlog(self, capacity=None):
         p = self.p
         cap = capacity or (self.outer + 1)
@@ -534,6 +562,118 @@ def synthesize(d, codes, grid, spatial_dims=2, crop=False, ctx=None):
     if crop:
         out = out[tuple(slice(s // 2, gg - s // 2) for s, gg in zip(sp, grid))]
     return out
+
+
+def threshold_sweep(d, codes, b, eps, grid, spatial_dims=2, ctx=None):
+    """Sweep candidate thresholds over sparse codes against the data in one pass on the GPU
+    (csrc/sweep_codes.hip): for every ``eps[e]`` and column ``j``, the number of entries with
+    ``not (abs(v) <= eps[e])``, their l1 mass, and ``sum (b - R_e)**2`` where ``R_e`` is what
+    ``synthesize`` gives for those entries alone (never stored).
+
+    ``d``, ``codes``, ``grid``, ``spatial_dims``: as for ``synthesize``.  ``b``: the data,
+    ``grid + channels + (n,)`` (everything is compared) or the interior
+    ``[g - 2 r ...] + channels + (n,)`` (what ``synthesize(crop=True)`` returns; the learners'
+    ``b``); any other shape is a ``ValueError``.  ``eps``: one or more thresholds, any order.
+    Returns ``{"eps", "nnz", "l1", "sse"}``: ``eps`` as given (float64, NumPy), the others
+    ``[E, n]`` (int64, float64, float64).  NumPy codes go through ccsc_threshold_sweep and NumPy
+    arrays come back; CUDA tensors go through ccsc_threshold_sweep_dev and the three arrays
+    stay on the device.  Every result is bitwise reproducible and independent of the other
+    columns and thresholds of the call.  ``ctx``: a one-device Context (default: a temporary
+    one)."""
+    lib = L.lib()
+    jc, ir, pr, (M, n), on_dev = _codes_triple(codes)
+    if spatial_dims not in (2, 3) or len(grid) != spatial_dims:
+        raise ValueError("grid has spatial_dims (2 or 3) extents")
+    if d.ndim < spatial_dims + 1:
+        raise ValueError("d is [s, s, (s), channels..., K]")
+    dshape = tuple(int(v) for v in d.shape)
+    sp, chan, K = dshape[:spatial_dims], dshape[spatial_dims:-1], dshape[-1]
+    Cn = int(np.prod(chan, dtype=np.int64)) if chan else 1
+    grid = tuple(int(v) for v in grid)
+    g3 = grid + (1,) * (3 - spatial_dims)
+    ks3 = sp + (1,) * (3 - spatial_dims)
+    if M != g3[0] * g3[1] * g3[2] * K:
+        raise ValueError(f"codes have {M} rows; grid {grid} with K = {K} has "
+                         f"{g3[0] * g3[1] * g3[2] * K}")
+    full = grid + chan + (n,)
+    inner = tuple(gg - 2 * (s // 2) for s, gg in zip(sp, grid)) + chan + (n,)
+    bshape = tuple(int(v) for v in b.shape)
+    if bshape == full:          # (the same region when every ks is 1)
+        crop = 0
+    elif bshape == inner:
+        crop = 1
+    else:
+        raise ValueError(f"b has shape {bshape}; the grid with its channels and columns is "
+                         f"{full}, its interior {inner}")
+    ev = np.ascontiguousarray(np.atleast_1d(np.asarray(eps, dtype=np.float64)))
+    if ev.ndim != 1 or ev.size < 1:
+        raise ValueError("eps is one threshold or a non-empty vector of them")
+    E = int(ev.size)
+    g_c, ks_c = (C.c_int32 * 3)(*g3), (C.c_int32 * 3)(*ks3)
+    nnz = int(ir.shape[0])
+    own = ctx is None
+    eb = L.errbuf()
+    if on_dev:
+        import torch
+        device = pr.device
+        dt = d if hasattr(d, "is_cuda") else torch.from_numpy(np.asarray(d, dtype=np.float64))
+        dt = dt.to(device=device, dtype=torch.float64)
+        dcol = dt.permute(*reversed(range(dt.ndim))).contiguous()    # column-major memory
+        bt = b if hasattr(b, "is_cuda") else torch.from_numpy(np.asarray(b, dtype=np.float64))
+        bt = bt.to(device=device, dtype=torch.float64)
+        bcol = bt.permute(*reversed(range(bt.ndim))).contiguous()
+        cnt = torch.zeros((n, E), dtype=torch.int64, device=device)   # [E, n], e fastest
+        l1 = torch.zeros((n, E), dtype=torch.float64, device=device)
+        sse = torch.zeros((n, E), dtype=torch.float64, device=device)
+        if own:
+            ctx = Context(device.index if device.index is not None
+                          else torch.cuda.current_device())
+        try:
+            torch.cuda.synchronize(device)
+            L.check(lib.ccsc_threshold_sweep_dev(
+                ctx.ptr, dcol.data_ptr(), ks_c, Cn, K, g_c, jc.data_ptr(), ir.data_ptr(),
+                pr.data_ptr(), n, nnz, bcol.data_ptr(), crop, L.dptr(ev), E, cnt.data_ptr(),
+                l1.data_ptr(), sse.data_ptr(), eb, len(eb)), eb)
+        finally:
+            if own:
+                ctx.close()
+        return {"eps": ev, "nnz": cnt.t(), "l1": l1.t(), "sse": sse.t()}
+    dh = np.asfortranarray(d, dtype=np.float64)
+    bh = np.asfortranarray(b.cpu().numpy() if hasattr(b, "is_cuda") else b, dtype=np.float64)
+    cnt = np.zeros((E, n), dtype=np.int64, order="F")
+    l1 = np.zeros((E, n), order="F")
+    sse = np.zeros((E, n), order="F")
+    if own:
+        import torch
+        ctx = Context(torch.cuda.current_device())
+    try:
+        L.check(lib.ccsc_threshold_sweep(
+            ctx.ptr, L.dptr(dh), ks_c, Cn, K, g_c, L.lptr(jc), L.lptr(ir), L.dptr(pr), n, nnz,
+            L.dptr(bh), crop, L.dptr(ev), E, L.lptr(cnt), L.dptr(l1), L.dptr(sse), eb, len(eb)),
+            eb)
+    finally:
+        if own:
+            ctx.close()
+    return {"eps": ev, "nnz": cnt, "l1": l1, "sse": sse}
+
+
+def pick_eps(sweep, rel):
+    """The threshold to keep from a ``threshold_sweep`` result: the largest ``eps`` whose
+    squared error, summed over the columns, is at most ``(1 + rel)`` times the total at the
+    smallest threshold of the sweep; the smallest threshold when no other qualifies (or when
+    that total is NaN).  Pure NumPy."""
+    eps = np.asarray(sweep["eps"], dtype=np.float64).reshape(-1)
+    sse = sweep["sse"]
+    sse = np.asarray(sse.cpu().numpy() if hasattr(sse, "is_cuda") else sse, dtype=np.float64)
+    if eps.size < 1 or sse.shape[0] != eps.size:
+        raise ValueError("sweep['sse'] has one row per threshold of sweep['eps']")
+    if not rel >= 0:
+        raise ValueError("rel must be >= 0")
+    total = sse.reshape(eps.size, -1).sum(axis=1)
+    base = int(np.argmin(eps))
+    ok = total <= (1.0 + rel) * total[base]
+    ok[base] = True
+    return float(eps[ok].max())
 
 
 def densify(codes, ctx=None):

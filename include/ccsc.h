@@ -570,6 +570,58 @@ int32_t ccsc_test_synth_index(const int32_t* g, const int32_t* ks, int32_t C, in
                               const int32_t* p, int32_t c, int64_t col, int64_t* out8, char* err,
                               size_t errlen);
 
+/* Threshold sweep of sparse codes against the data: how an eps for ccsc_session_codes_* /
+ * ccsc_sparsify_* is chosen, in one pass over the entries instead of one ccsc_synthesize and
+ * one dense reconstruction per candidate.  d, ks, C, K, g, jc, ir, pr, n, nnz: as for
+ * ccsc_synthesize.  eps[E], E >= 1: the candidate thresholds, in any order, duplicates,
+ * negative values (which keep stored zeros too) and +-inf allowed, a NaN is CCSC_E_INVALID.
+ * For threshold e and column j, with "kept" meaning !(|pr| <= eps[e]) -- the predicate of the
+ * threshold-and-compact, so a NaN value is kept at every threshold:
+ *   nnz_out[e + E j] = the number of kept entries of column j            (int64)
+ *   l1_out [e + E j] = sum |pr| over them                                (double)
+ *   sse_out[e + E j] = sum over the compared region of (b - R_e)^2       (double)
+ * R_e[x, y, t, c, j] is ccsc_synthesize's out for the kept entries alone -- the same embedding,
+ * each element from +0.0, one fma(value, tap, acc) per contributing kept entry in storage
+ * order, duplicates add -- so it has the bits ccsc_synthesize gives for the filtered triple;
+ * it is held in registers and never stored.
+ *   crop = 1: b is column-major [g0 - 2 r0, g1 - 2 r1, g2 - 2 r2, C, n] and the interior
+ *             r_a <= p_a < g_a - r_a of every axis is compared (the objectives' Dz against the
+ *             learners' b; the 2-3D learner's b minus smooth_init);
+ *   crop = 0: b is [g0, g1, g2, C, n] and every element is compared.
+ * A column without entries, or with none kept, has sse = sum b^2 (in the order below) and
+ * l1 = +0.0.  Results come back in the caller's order of eps and do not depend on the other
+ * thresholds of the call: the thresholds are sorted and served eight per launch, and a
+ * threshold's sums involve its own kept entries only.
+ * Order of the sums (no floating-point atomics): inside a workgroup -- one 16 x 16 tile of a
+ * t-plane and four channels -- each thread sums its channels in order, a fixed tree joins the
+ * threads, and a second kernel adds a column's workgroup partials in block order; nnz is exact
+ * and l1 is summed in a fixed order of the column's entries.  So a column's three results are
+ * the same bits alone or in any batch, for every chunking, and for both forms.
+ * Validation (before the device is touched and before the context check): that of
+ * ccsc_synthesize, then CCSC_E_INVALID for a NULL b, eps or output (b and the outputs only
+ * when n > 0), E < 1 and a NaN threshold.  One-device context only; n == 0 is CCSC_OK.  A
+ * malformed matrix is skipped on the device and gives CCSC_E_INVALID as for ccsc_synthesize.
+ * The host form takes host arrays and stages columns in chunks (16 B per entry, the column's
+ * slice of b, 24 B per threshold and column, 64 B per workgroup) within 256 MiB or
+ * CCSC_CODES_WS_MB; the _dev form takes every array but ks, g and eps on the context's device,
+ * runs ordered on its stream and is synchronised on return.  Workspace is allocated inside
+ * the call and freed before it returns (ccsc_plan_bytes is unchanged). */
+int32_t ccsc_threshold_sweep(ccsc_ctx* ctx, const double* d, const int32_t* ks, int32_t C,
+                             int32_t K, const int32_t* g, const int64_t* jc, const int64_t* ir,
+                             const double* pr, int64_t n, int64_t nnz, const double* b,
+                             int32_t crop, const double* eps, int32_t E, int64_t* nnz_out,
+                             double* l1_out, double* sse_out, char* err, size_t errlen);
+int32_t ccsc_threshold_sweep_dev(ccsc_ctx* ctx, const double* d, const int32_t* ks, int32_t C,
+                                 int32_t K, const int32_t* g, const int64_t* jc,
+                                 const int64_t* ir, const double* pr, int64_t n, int64_t nnz,
+                                 const double* b, int32_t crop, const double* eps, int32_t E,
+                                 int64_t* nnz_out, double* l1_out, double* sse_out, char* err,
+                                 size_t errlen);
+/* Host only: the threshold class the sweep's kernels give a value -- *m = the number of
+ * thresholds of eps[E] that v survives, through the same sort, grouping and inline function. */
+int32_t ccsc_test_sweep_class(const double* eps, int32_t E, double v, int32_t* m, char* err,
+                              size_t errlen);
+
 /* ---- kernel-level entry points (parity tests of single stages) ---------- */
 /* 2D R2C of `count` real slices [X,Y] -> half spectra [Y][X/2+1] (re,im). */
 int32_t ccsc_test_fft2d(ccsc_ctx* ctx, int32_t X, int32_t Y, int32_t count, const double* in,
